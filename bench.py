@@ -8,7 +8,9 @@ A step = CL(ABMIL) forward on both views (128 bag-forwards) -> Full_layer GRU st
 timed region.  With N > 1 GPUs each rank owns 64 bags (weak scaling); embeddings are
 all-gathered for the global contrastive denominator and gradients all-reduced (RCCL).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run measures the headline only (set-up, warm-up, the K timed steps); --full adds
+everything measured beside it (box calibration, roofline, the eager region beside the graph one, step statistics, comm, the
+extras); --dump-outputs DIR writes the loss and the updated parameters of the last timed step as DIR/<name>.npy.
 """
 import argparse
 import gc
@@ -433,7 +435,7 @@ def graph_timed_region(step, opt, steps, barrier):
     captured one again - and the region is steps / G replays bracketed like the eager one.  No host work sits between the launches of a
     step: one host stall cannot land in a 20-step window (it cost the driver's round-5 line 2-5 %, and an 8.9 ms one 25 % in round 4).
     G = the largest of (10, 5, 4, 2, 1) that divides ``steps`` (a replay costs ~10-16 us to start: amortised over G steps).
-    -> dict(ms_per_step, elapsed_s, steps_per_graph, replays, per-replay statistics)."""
+    -> (dict(ms_per_step, elapsed_s, steps_per_graph, replays, per-replay statistics), the loss of the last replayed step)."""
     G = next(g for g in (10, 5, 4, 2, 1) if steps % g == 0)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
@@ -447,7 +449,7 @@ def graph_timed_region(step, opt, steps, barrier):
     try:
         with torch.cuda.graph(g, stream=s):
             for _ in range(G):
-                step()
+                loss = step()                                # the graph's own output: after a replay it holds that replay's last loss
     except Exception:
         opt.live_graph(False)
         raise
@@ -471,7 +473,7 @@ def graph_timed_region(step, opt, steps, barrier):
     return dict(ms_per_step=elapsed / steps * 1e3, elapsed_s=elapsed, steps_per_graph=G, replays=n_rep,
                 per_replay_ms_per_step=dict(median=round(per[len(per) // 2], 4), min=round(per[0], 4), max=round(per[-1], 4)),
                 note="G steps captured once, replayed steps / G times; Adam's step counts live on the device (murcl_adam_multi_live): every "
-                     "replayed step is the next optimizer step")
+                     "replayed step is the next optimizer step"), loss
 
 
 def launch_argv(gpus, argv, port=None):
@@ -604,7 +606,28 @@ def self_launch(gpus, argv):
     return subprocess.run(launch_argv(gpus, argv), env=env, cwd=ROOT).returncode
 
 
-SETTLE_STEPS = 30          # untimed steps (warm-up + breakdown pass + extra) that precede the timed region at the least
+SETTLE_STEPS = 30          # untimed steps (warm-up + breakdown pass + extra) that precede the eager timed region at the least
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def collect_outputs(loss, modules):
+    """What a caller of the timed step holds after it: the loss and the updated parameters of every module in ``modules``
+    ({prefix: module}), copied to the host as float32 arrays (23 MiB for the headline's model, whatever the input shape)."""
+    arrays = {"loss": loss}
+    for prefix, mod in modules.items():
+        arrays.update({f"{prefix}.{k}": p for k, p in mod.named_parameters()})
+    return {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+
+
+def write_outputs(dirname, arrays):
+    """--dump-outputs: ``arrays`` as ``dirname/<name>.npy``, at most DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the limit of {DUMP_LIMIT_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
 
 
 def main():
@@ -612,18 +635,30 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--stat-steps", type=int, default=100, help="steps of the per-step HIP-event statistics pass (0 = off)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: box calibration, per-kernel breakdown and roofline, the eager "
+                         "region beside the graph one, step statistics, comm diagnostics and the extras (f32 path, M-full, rows, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the loss and the updated parameters of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--stat-steps", type=int, default=100, help="(--full) steps of the per-step HIP-event statistics pass (0 = off)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--bags", type=int, default=64)
     ap.add_argument("--patches", type=int, default=2048)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the extras that follow the headline")
     ap.add_argument("--graph", action=argparse.BooleanOptionalAction, default=True,
-                    help="after the timed region, capture one step as a hipGraph and report ms_per_step_graph (single GPU)")
-    ap.add_argument("--breakdown", action="store_true", help="print the per-kernel table to stderr")
+                    help="time the K steps as hipGraph replays (single GPU); --no-graph times them as steps enqueued from Python")
+    ap.add_argument("--breakdown", action="store_true", help="(--full) print the per-kernel table to stderr")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.breakdown and not args.full:
+        ap.error("--breakdown needs --full")
 
     if (args.gpus > 1 or os.environ.get("MURCL_BENCH_SPAWN") == "1") and "WORLD_SIZE" not in os.environ:
-        sys.exit(self_launch(args.gpus, sys.argv[1:]))
+        argv = sys.argv[1:]
+        if args.dump_outputs:                         # the ranks run from the repository root: hand them an absolute directory
+            argv = argv + ["--dump-outputs", os.path.abspath(args.dump_outputs)]
+        sys.exit(self_launch(args.gpus, argv))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -648,6 +683,7 @@ def main():
     model, fc, opt, crit = build(dtype, device, B)
     views = synth_views(B, N, D, dtype, device, rank)
     step = make_step(model, fc, opt, crit, views, 2 if force_dist else world)
+    want_outputs = bool(args.dump_outputs) and rank == 0
 
     def barrier():
         if world > 1 or force_dist:
@@ -665,7 +701,7 @@ def main():
     gc.collect()
     gc.freeze()
     box = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             box = box_calibration(device)
         except Exception as e:                                                 # noqa: BLE001  (a diagnostic must not take the line with it)
@@ -673,52 +709,66 @@ def main():
     for _ in range(max(0, args.warmup - 1)):
         step()
 
-    # -- breakdown pass (untimed): find the kernel that dominates the step
-    ops.TIMERS = ops.KernelTimers()
-    for _ in range(2):
-        step()
-    torch.cuda.synchronize()
-    breakdown = ops.TIMERS.summary()
-    ops.TIMERS = None
-    dominant = max(breakdown, key=lambda k: breakdown[k]["ms_total"])
     k2_key = f"abmil_pool_fwd<{args.dtype}>"
-
-    # -- timed region: exactly K steps; only the dominant kernel and K2 carry HIP events, on every third launch
     k2row_key = f"row:k2_fwd<{args.dtype}>"             # the K2 row of the step: ONE launch since round 6 (its per-bag merge is inside the decoder launch)
-    ops.TIMERS = ops.KernelTimers(only={dominant, k2row_key}, every=3, pool=6 * (args.steps + 40))
-    # settle: untimed steps (in the timed region's configuration) back to back right up to the barrier that opens it, so
-    # that at least SETTLE_STEPS steps precede the timed ones whatever --warmup says and the few milliseconds of host work
-    # above (reading the breakdown events) are not the last thing the GPU saw
-    warmup_extra = max(10, SETTLE_STEPS - args.warmup - 2)
-    for _ in range(warmup_extra):
-        step()
-    ops.TIMERS.reset()
-    diag = os.environ.get("MURCL_BENCH_DIAG") == "1"          # dev: one HIP event per timed step (where does a short region lose time?)
-    devs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if diag else None
-    barrier()
-    t0 = time.perf_counter()
-    host_t = [t0]
-    if diag:
-        devs[0].record()
-    for i in range(args.steps):
-        loss = step()
+
+    def eager_region():
+        """The K steps enqueued step by step from Python between two barriers, after 2 + ``warmup_extra`` untimed ones.  Under --full
+        the 2 are the per-kernel breakdown pass, and the dominant kernel and K2 carry HIP events in the timed steps."""
+        r = {}
+        # -- breakdown pass (untimed): find the kernel that dominates the step
+        if args.full:
+            ops.TIMERS = ops.KernelTimers()
+        for _ in range(2):
+            step()
+        if args.full:
+            torch.cuda.synchronize()
+            r["breakdown"] = ops.TIMERS.summary()
+            r["dominant"] = max(r["breakdown"], key=lambda k: r["breakdown"][k]["ms_total"])
+            # -- timed region: exactly K steps; only the dominant kernel and K2 carry HIP events, on every third launch
+            ops.TIMERS = ops.KernelTimers(only={r["dominant"], k2row_key}, every=3, pool=6 * (args.steps + 40))
+        # settle: untimed steps (in the timed region's configuration) back to back right up to the barrier that opens it, so
+        # that at least SETTLE_STEPS steps precede the timed ones whatever --warmup says and the few milliseconds of host work
+        # above (reading the breakdown events) are not the last thing the GPU saw
+        r["warmup_extra"] = max(10, SETTLE_STEPS - args.warmup - 2)
+        for _ in range(r["warmup_extra"]):
+            step()
+        if args.full:
+            ops.TIMERS.reset()
+        diag = os.environ.get("MURCL_BENCH_DIAG") == "1"          # dev: one HIP event per timed step (where does a short region lose time?)
+        devs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if diag else None
+        barrier()
+        t0 = time.perf_counter()
+        host_t = [t0]
         if diag:
-            devs[i + 1].record()
-        host_t.append(time.perf_counter())
-    barrier()
-    elapsed = time.perf_counter() - t0
-    if diag and rank == 0:
-        per = [devs[i].elapsed_time(devs[i + 1]) for i in range(args.steps)]
-        print("DIAG gpu ms per timed step:", [round(p, 3) for p in per], file=sys.stderr)
-        print("DIAG host ms per timed step:", [round((host_t[i + 1] - host_t[i]) * 1e3, 2) for i in range(args.steps)], file=sys.stderr)
-        print("DIAG elapsed", round(elapsed * 1e3, 3), "sum gpu", round(sum(per), 3), file=sys.stderr)
-    host_ms = [(host_t[i + 1] - host_t[i]) * 1e3 for i in range(args.steps)]
-    live = ops.TIMERS.summary()
-    ops.TIMERS = None
+            devs[0].record()
+        for i in range(args.steps):
+            loss = step()
+            if diag:
+                devs[i + 1].record()
+            host_t.append(time.perf_counter())
+        barrier()
+        elapsed = time.perf_counter() - t0
+        if diag and rank == 0:
+            per = [devs[i].elapsed_time(devs[i + 1]) for i in range(args.steps)]
+            print("DIAG gpu ms per timed step:", [round(p, 3) for p in per], file=sys.stderr)
+            print("DIAG host ms per timed step:", [round((host_t[i + 1] - host_t[i]) * 1e3, 2) for i in range(args.steps)], file=sys.stderr)
+            print("DIAG elapsed", round(elapsed * 1e3, 3), "sum gpu", round(sum(per), 3), file=sys.stderr)
+        if args.full:
+            r["live"] = ops.TIMERS.summary()
+            ops.TIMERS = None
+        # copied now: under --full more steps follow (statistics pass, comm diagnostics, the graph region)
+        r["outputs"] = collect_outputs(loss, {"model": model, "fc": fc}) if want_outputs else None
+        r.update(loss=loss, elapsed=elapsed, t0=t0, host_t=host_t)
+        return r
+
+    use_graph = world == 1 and not force_dist and args.graph
+    # a plain run times only the region `value` comes from; --full times the eager region in any case
+    E = eager_region() if args.full or not use_graph else None
     # -- statistics pass (outside the timed region): per-step HIP-event durations on the launch stream, no kernel timers,
     #    every rank takes part (the steps contain collectives).  median / p10 / p90 go out beside the headline value.
     stats = None
-    if args.stat_steps > 0:
+    if args.full and args.stat_steps > 0:
         evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.stat_steps + 1)]
         barrier()
         evs[0].record()
@@ -730,12 +780,12 @@ def main():
         q = lambda f: per[min(len(per) - 1, int(f * len(per)))]  # noqa: E731
         stats = dict(steps=args.stat_steps, median_ms=round(q(0.5), 4), p10_ms=round(q(0.1), 4), p90_ms=round(q(0.9), 4),
                      min_ms=round(per[0], 4), max_ms=round(per[-1], 4), timing="HIP events on the launch stream, one per step")
-    if world > 1:
-        t = torch.tensor([elapsed], device=device, dtype=torch.float64)
+    if E is not None and world > 1:
+        t = torch.tensor([E["elapsed"]], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = t.item()
+        E["elapsed"] = t.item()
     comm = None
-    if world > 1 or force_dist:
+    if args.full and (world > 1 or force_dist):
         try:
             comm = comm_diagnostics(model, fc, opt, crit, views, world, device)
         except Exception as e:                                                 # noqa: BLE001  (diagnostics must not take the line with them)
@@ -744,30 +794,110 @@ def main():
         dist.destroy_process_group()
         return
 
-    ms_step = elapsed / args.steps * 1e3
-    value = B * world / (elapsed / args.steps)
-    eager = dict(value=round(value, 2), ms_per_step=round(ms_step, 4),
-                 note="K steps enqueued step by step from Python between the same barriers (the per-kernel HIP events of `roofline` were taken in this region)")
-    timing_mode = "eager: K steps enqueued from Python (the host runs ~0.6 ms per step ahead of the GPU)"
+    def eager_headline():
+        ms, v = E["elapsed"] / args.steps * 1e3, B * world / (E["elapsed"] / args.steps)
+        return (v, ms, E["loss"], E["outputs"],
+                dict(value=round(v, 2), ms_per_step=round(ms, 4),
+                     note="K steps enqueued step by step from Python between the same barriers (the per-kernel HIP events of `roofline` were taken in this region)"),
+                "eager: K steps enqueued from Python (the host runs ~0.6 ms per step ahead of the GPU)")
+    value = ms_step = loss = outputs = eager = timing_mode = None
+    if E is not None:
+        value, ms_step, loss, outputs, eager, timing_mode = eager_headline()
     graph = None
-    if world == 1 and not force_dist and args.graph:
-        # a SECOND region of exactly K steps, as hipGraph replays with live optimizer state (round 6: every replayed step is a real
-        # training step, Adam's step counts advance on the device).  It is GPU-paced: the host launches K / G graphs and waits.  The
-        # eager region is host-paced whenever the host is slower than the GPU - measured on this pool: a loaded host (four tenants per
-        # box) enqueued a step in 1.56 ms instead of 0.8 and the eager region read 1.958 ms per step while the GPU needed 1.45
-        # (gpurun_out/r06_zz_bench_driver_args2.json), and in a 20-step window the first step alone runs from an empty queue (+ 1-2 %).
-        # With a healthy host the two regions agree to 0.5 % (profiles/r06_zz_bench*.json).  `value` is therefore the graph region
-        # when it exists ("make value robust to one host stall ... the graph replay once its arguments are live"),
-        # and the eager region is reported beside it; --no-graph, more than one rank, or a capture failure leave `value` eager.
+    if use_graph:
+        # a region of exactly K steps as hipGraph replays with live optimizer state (round 6: every replayed step is a real training
+        # step, Adam's step counts advance on the device).  It is GPU-paced: the host launches K / G graphs and waits.  The eager
+        # region (--full: the same K steps before it) is host-paced whenever the host is slower than the GPU - measured on this pool:
+        # a loaded host (four tenants per box) enqueued a step in 1.56 ms instead of 0.8 and the eager region read 1.958 ms per step
+        # while the GPU needed 1.45 (profiles/r06_q_bench_loaded_host.json), and in a 20-step window the first step alone runs from
+        # an empty queue (+ 1-2 %).  With a healthy host the two regions agree to 0.5 % (profiles/r06_zz_bench*.json).  `value` is
+        # therefore the graph region when it exists ("make value robust to one host stall ... the graph replay once
+        # its arguments are live"); --no-graph, more than one rank, or a capture failure leave `value` eager.
         try:
-            graph = graph_timed_region(step, opt, args.steps, barrier)
+            graph, g_loss = graph_timed_region(step, opt, args.steps, barrier)
             graph["ms_per_step_graph"] = round(graph["ms_per_step"], 4)
             graph["value_graph"] = round(B * world / (graph["elapsed_s"] / args.steps), 2)
-            value, ms_step = B * world / (graph["elapsed_s"] / args.steps), graph["ms_per_step"]
+            value, ms_step, loss = B * world / (graph["elapsed_s"] / args.steps), graph["ms_per_step"], g_loss
+            outputs = collect_outputs(loss, {"model": model, "fc": fc}) if want_outputs else None
             timing_mode = ("hipgraph: the K steps as replays of captured graphs of G steps with LIVE optimizer state, between the same "
-                           "barriers (GPU-paced; the eager region of the same K steps - `eager` - is host-paced when the host is loaded)")
-        except Exception as e:                                                 # noqa: BLE001  (a diagnostic must not take the line with it)
+                           "barriers (GPU-paced; the eager region of the same K steps - `eager`, --full - is host-paced when the host is loaded)")
+        except Exception as e:                                                 # noqa: BLE001  (the eager region stands in for it)
             graph = {"error": f"{type(e).__name__}: {e}"[:300]}
+            print(f"bench.py: graph region failed, timing the eager region instead: {e!r}", file=sys.stderr, flush=True)
+            if E is None:
+                E = eager_region()
+                value, ms_step, loss, outputs, eager, timing_mode = eager_headline()
+    if want_outputs:
+        write_outputs(args.dump_outputs, outputs)
+
+    out = {
+        "metric": "WSI-bags/sec pretrain step (ABMIL+NT-Xent) at N=2048,d=512",
+        "value": round(value, 2), "unit": "bags/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 4), "timing_mode": timing_mode,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": args.dtype, "data": "synthetic",
+        "precision_note": ("bf16 storage of patch-level tensors, f32 accumulation and f32 bag-level math: checked against the f32 kernels to ~2e-2 "
+                           "(outputs <= 2 % of max, attention <= 3-5 % rel, gradients <= 5 % norm-wise, 40-step loss trajectories within 2 %: "
+                           "tests/test_gpu_modules.py, test_gpu_step.py); the f32 kernels are the ones held to 1e-4 against the reference") if args.dtype == "bf16" else
+                          "f32 parity path: <= 1e-4 against outputs of the reference (tests/golden)",
+        "config": {"workload": f"ABMIL+Full_layer+NT-Xent view-pair pretrain step (fwd+bwd+Adam), {B} bags x {N} x {D} "
+                               f"per GPU, {args.dtype} patch tensors / f32 accumulate (BASELINE configs[1])",
+                   "bags_per_gpu": B, "patches": N, "feat_dim": D, "global_bags": B * world,
+                   "sharding": "bags by WSI; all-gather of z + grad all-reduce" if world > 1 else "single GPU"},
+        "full": args.full,
+        "graph": graph,
+        "ms_per_step_graph": graph.get("ms_per_step_graph") if graph else None,
+        "loss": round(float(loss.item()), 6),
+    }
+    if E is not None:
+        out.update({
+            "warmup_extra": E["warmup_extra"] + 2,
+            "warmup_note": f"W={args.warmup} warm-up steps as asked, then {E['warmup_extra'] + 2} more untimed steps (2 of them the per-kernel breakdown "
+                           f"pass under --full, the rest right up to the barrier that opens the eager region) so that >= {SETTLE_STEPS} steps precede "
+                           "its timed ones: the first ~10 steps after an idle GPU run 14 % slower",
+            "eager": eager, "ms_per_step_eager": eager["ms_per_step"],
+            # eager slower than the GPU-paced region by more than 3 %: the host, not the GPU, paced the eager region - its per-kernel HIP
+            # events (`roofline`, `roofline_k2`) then include the GPU's wait for late launches and read low
+            "eager_host_paced": (bool(eager["ms_per_step"] > 1.03 * graph["ms_per_step"]) if graph and "ms_per_step" in graph else None),
+        })
+    if args.full:
+        out.update(full_diagnostics(args, E, box, ms_step, B, N, D, k2_key, k2row_key))
+        out.update(comm=comm, step_stats=stats,
+                   bags_per_s_at_median=round(B * world / (stats["median_ms"] * 1e-3), 1) if stats else None)
+    if args.full and world == 1 and not args.no_cpu_baseline:
+        del model, fc, opt, views, step                    # free the headline step's activations before the second workload
+        gc.collect()
+        torch.cuda.empty_cache()
+        # the extras run after the headline has been measured: a failure in one of them is recorded, it must not take the
+        # contract's JSON line with it
+        def extra(name, fn):
+            try:
+                out[name] = fn()
+            except Exception as e:                                   # noqa: BLE001
+                out[name] = {"error": f"{type(e).__name__}: {e}"[:300]}
+                print(f"bench.py: extra '{name}' failed: {e!r}", file=sys.stderr, flush=True)
+            gc.collect()
+            torch.cuda.empty_cache()
+        extra("abmil_c2_f32", lambda: headline_f32(device, B, N, D))
+        extra("m_full", lambda: m_full(device, dtype))
+        extra("rows", lambda: other_rows(device))
+        extra("cpu_baseline", lambda: cpu_baseline(B, N, D))
+    if args.breakdown:
+        for k, v in sorted(E["breakdown"].items(), key=lambda kv: -kv[1]["ms_total"]):
+            print(f"{k:44s} calls/step {v['calls'] // 2:3d}  ms/step {v['ms_total'] / 2:8.4f}", file=sys.stderr)
+    if world > 1 or force_dist:
+        dist.destroy_process_group()
+    import ctypes
+    ctypes.CDLL(None).fflush(None)          # RCCL's banner sits in the C stdio buffer: push it out BEFORE the result line
+    print(json.dumps(out), flush=True)
+
+
+def full_diagnostics(args, E, box, ms_step, B, N, D, k2_key, k2row_key):
+    """--full: the roofline of the dominant kernel and of the K2 row (their HIP events in the eager region), the step against SURVEY
+    8(d), the box calibration and every encoder-sized launch against it, the per-kernel table of the breakdown pass."""
+    breakdown, live, dominant = E["breakdown"], E["live"], E["dominant"]
+    elapsed, host_t, t0 = E["elapsed"], E["host_t"], E["t0"]
+    host_ms = [(host_t[i + 1] - host_t[i]) * 1e3 for i in range(args.steps)]
 
     # SURVEY 8(d) classifies the kernels: the encoder-sized GEMMs (K1: forward, input gradients, weight gradients) are MFMA-bound
     # (a fused encoder moves X once: intensity ~1.7 kFLOP/B), K2 and the streaming passes are HBM-bound.  The layer-wise bytes of a
@@ -835,27 +965,7 @@ def main():
                    note="hbm_bytes_pmc sums the encoder-sized kernels only (the bag-level head moves < 3 % of the step's bytes)")
         return out
 
-    out = {
-        "metric": "WSI-bags/sec pretrain step (ABMIL+NT-Xent) at N=2048,d=512",
-        "value": round(value, 2), "unit": "bags/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "warmup_extra": warmup_extra + 2,
-        "warmup_note": f"W={args.warmup} warm-up steps as asked, then {warmup_extra + 2} more untimed steps (2 of them the per-kernel breakdown "
-                       f"pass, the rest right up to the barrier that opens the timed region) so that >= {SETTLE_STEPS} steps precede the timed ones: "
-                       "the first ~10 steps after an idle GPU run 14 % slower",
-        "ms_per_step": round(ms_step, 4), "timing_mode": timing_mode, "eager": eager,
-        # eager slower than the GPU-paced region by more than 3 %: the host, not the GPU, paced the eager region - its per-kernel HIP
-        # events (`roofline`, `roofline_k2`) then include the GPU's wait for late launches and read low
-        "eager_host_paced": (bool(eager["ms_per_step"] > 1.03 * graph["ms_per_step"]) if graph and "ms_per_step" in graph else None),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": args.dtype, "data": "synthetic",
-        "precision_note": ("bf16 storage of patch-level tensors, f32 accumulation and f32 bag-level math: checked against the f32 kernels to ~2e-2 "
-                           "(outputs <= 2 % of max, attention <= 3-5 % rel, gradients <= 5 % norm-wise, 40-step loss trajectories within 2 %: "
-                           "tests/test_gpu_modules.py, test_gpu_step.py); the f32 kernels are the ones held to 1e-4 against the reference") if args.dtype == "bf16" else
-                          "f32 parity path: <= 1e-4 against outputs of the reference (tests/golden)",
-        "config": {"workload": f"ABMIL+Full_layer+NT-Xent view-pair pretrain step (fwd+bwd+Adam), {B} bags x {N} x {D} "
-                               f"per GPU, {args.dtype} patch tensors / f32 accumulate (BASELINE configs[1])",
-                   "bags_per_gpu": B, "patches": N, "feat_dim": D, "global_bags": B * world,
-                   "sharding": "bags by WSI; all-gather of z + grad all-reduce" if world > 1 else "single GPU"},
+    return {
         "box": box,
         "roofline": dict(roof(dominant), step=step_roof()),
         "roofline_k2": dict(roof(k2row_key), kernel=k2_key, launches_of_the_row=[k2_key],
@@ -866,15 +976,8 @@ def main():
                                  "<= 8 chunk partials happens while the decoder product loads its A operand (merge_launch: one launch where "
                                  "rounds 1-5 ran a combine launch and a GEMM), the normalised attention rows come out of the backward pass; "
                                  "avg_launch_ms = one HIP-event pair around the launch inside the timed region (~2.5 us of record cost included)"),
-        "comm": comm,
-        "graph": graph,
-        "ms_per_step_graph": graph.get("ms_per_step_graph") if graph else None,
-        "ms_per_step_eager": eager["ms_per_step"],
-        "loss": round(float(loss.item()), 6),
-        "step_stats": stats,
         "timed_region_host_enqueue_ms": {"median": round(sorted(host_ms)[len(host_ms) // 2], 3), "max": round(max(host_ms), 3),
                                          "drain_after_last_enqueue": round((elapsed - (host_t[-1] - t0)) * 1e3, 3)},
-        "bags_per_s_at_median": round(B * world / (stats["median_ms"] * 1e-3), 1) if stats else None,
         "kernels_vs_box": {k: dict(us=round(v["ms_avg"] * 1e3, 1), layer_GBps=round(v["bytes"] / v["calls"] / (v["ms_avg"] * 1e-3) / 1e9, 1),
                                    frac_of_box_copy=round(v["bytes"] / v["calls"] / (v["ms_avg"] * 1e-3) / 1e9 / box["copy_GBps"], 3),
                                    TFLOPs=round(v["flops"] / v["calls"] / (v["ms_avg"] * 1e-3) / 1e12, 1),
@@ -886,32 +989,6 @@ def main():
         "kernel_ms_per_step_note": "untimed 2-step pass with EVERY launch bracketed by HIP events (~2-3 us each): sums above ms_per_step",
         "kernel_ms_per_step": {k: round(v["ms_total"] / 2, 4) for k, v in sorted(breakdown.items(), key=lambda kv: -kv[1]["ms_total"])},
     }
-    if world == 1 and not args.no_cpu_baseline:
-        del model, fc, opt, views, step                    # free the headline step's activations before the second workload
-        gc.collect()
-        torch.cuda.empty_cache()
-        # the extras run after the headline has been measured: a failure in one of them is recorded, it must not take the
-        # contract's JSON line with it
-        def extra(name, fn):
-            try:
-                out[name] = fn()
-            except Exception as e:                                   # noqa: BLE001
-                out[name] = {"error": f"{type(e).__name__}: {e}"[:300]}
-                print(f"bench.py: extra '{name}' failed: {e!r}", file=sys.stderr, flush=True)
-            gc.collect()
-            torch.cuda.empty_cache()
-        extra("abmil_c2_f32", lambda: headline_f32(device, B, N, D))
-        extra("m_full", lambda: m_full(device, dtype))
-        extra("rows", lambda: other_rows(device))
-        extra("cpu_baseline", lambda: cpu_baseline(B, N, D))
-    if args.breakdown:
-        for k, v in sorted(breakdown.items(), key=lambda kv: -kv[1]["ms_total"]):
-            print(f"{k:44s} calls/step {v['calls'] // 2:3d}  ms/step {v['ms_total'] / 2:8.4f}", file=sys.stderr)
-    if world > 1 or force_dist:
-        dist.destroy_process_group()
-    import ctypes
-    ctypes.CDLL(None).fflush(None)          # RCCL's banner sits in the C stdio buffer: push it out BEFORE the result line
-    print(json.dumps(out), flush=True)
 
 
 def _pmc_traffic(key):

@@ -53,6 +53,10 @@ int murcl_gemm_tn(const void* A, const void* B, float* C, int M, int N1, int N2,
  * weight gradients (N1, N2 multiples of 256, M >= 16384) run on 256 x 256 tiles whose per-split partial sums go to the
  * workspace as plain stores and are added to C by a second launch - no float atomics; other shapes behave as murcl_gemm_tn. */
 long murcl_gemm_tn_workspace_bytes(int M, int N1, int N2, int dtype);
+/* Shapes with M >= 16384 rows that run on the 128 x 128 kernel with more than one M-split: given a workspace of at least
+ * murcl_gemm_tn_parts_bytes (0 = one split or another kernel), murcl_gemm_tn_ws stores each split's partial tile there and adds
+ * the splits to C (and colsum_out) in a fixed order by a second launch - the same result on every run. */
+long murcl_gemm_tn_parts_bytes(int M, int N1, int N2, int dtype);
 int murcl_gemm_tn_ws(const void* A, const void* B, float* C, int M, int N1, int N2, int lda, int ldb, int ldc, int dtype,
                      int splits, float* colsum_out, float* ws, long ws_bytes, const float* colsum_part, int colsum_rows,
                      murcl_stream_t stream);

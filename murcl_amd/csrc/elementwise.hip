@@ -254,7 +254,9 @@ extern "C" int murcl_colsum(const void* x, float* out, int R, int N, int ld, int
     if (N <= 0) return 0;
     const int bc = dtype == MURCL_DTYPE_BF16 ? 128 : 64;     // columns per block
     const int cg = (N + bc - 1) / bc;
-    int splits = R > 64 ? (1024 + cg - 1) / cg : 1;        // ~1024 blocks, >= 32 rows each, <= 64 adders per column
+    // bag-level row counts (<= 512) keep one writer per column: the same sum on every run (split rows meet through float
+    // atomics, in arrival order); longer columns are split: ~1024 blocks, >= 32 rows each, <= 64 adders per column
+    int splits = R > 512 ? (1024 + cg - 1) / cg : 1;
     if (splits > (R + 31) / 32) splits = (R + 31) / 32;
     if (splits > 64) splits = 64;
     if (splits < 1) splits = 1;

@@ -522,7 +522,7 @@ template <typename T, int NSLOT, bool X3 = false>
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ A, const T* __restrict__ B,
                                                          float* __restrict__ C, int M, int N1, int N2, int lda, int ldb,
                                                          int ldc, int m_per_split, int nsplit,
-                                                         float* __restrict__ colsum_out) {
+                                                         float* __restrict__ colsum_out, float* __restrict__ part) {
     typedef typename Frag<T>::type frag_t;
     typedef TnTraits<T> TT;
     // NSLOT = 2: double buffer per workgroup; TWO workgroups per CU desynchronise and cover each other's barrier /
@@ -688,7 +688,11 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ A
         compute(s);
     }
     // lane holds C[n1 = n10+wr*64+i*16+4q+r][n2 = n20+wc*64+j*16+(lane&15)]
+    // `part` (splits > 1 with a workspace): this split's partial tile is STORED to part[sp][n1][n2] (its column sums to
+    // part[nsplit][N1*N2 + ...]: see tn_split_reduce_kernel) and the splits are added in a fixed order by the reduce launch -
+    // the same result on every run, where float atomics add them in arrival order
     const int q4 = lane >> 4, r16 = lane & 15;
+    float* const P = part ? part + (size_t)sp * N1 * N2 : nullptr;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -697,7 +701,10 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ A
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int n1 = n10 + wr * 64 + i * 16 + 4 * q4 + r;
-                if (n1 < N1 && n2 < N2) atomicAdd(C + (size_t)n1 * ldc + n2, acc[i][j][r]);
+                if (n1 < N1 && n2 < N2) {
+                    if (P) P[(size_t)n1 * N2 + n2] = acc[i][j][r];
+                    else atomicAdd(C + (size_t)n1 * ldc + n2, acc[i][j][r]);
+                }
             }
         }
     if (do_cs && r16 == 0) {                   // one adder per column and M-split (<= 64 per address)
@@ -706,8 +713,52 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ A
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int n1 = n10 + wr * 64 + i * 16 + 4 * q4 + r;
-                if (n1 < N1) atomicAdd(colsum_out + n1, accs[i][r]);
+                if (n1 < N1) {
+                    if (part) part[(size_t)nsplit * N1 * N2 + (size_t)sp * N1 + n1] = accs[i][r];
+                    else atomicAdd(colsum_out + n1, accs[i][r]);
+                }
             }
+    }
+}
+
+// C[n1][n2] += sum over the splits of part[s][n1][n2] (and colsum_out[n1] += the splits' column sums, stored behind the
+// tiles): the fixed-order end of gemm_tn_kernel's split reduction.  A workgroup takes 32 elements; its 8 thread groups sum
+// consecutive eighths of the splits (loads in flight together), one thread adds the 8 group sums in order - the same
+// summation tree on every run, with 8x the threads of one summing thread per element.
+__global__ __launch_bounds__(256) void tn_split_reduce_kernel(const float* __restrict__ part, float* __restrict__ C,
+                                                              float* __restrict__ colsum_out, int N1, int N2, int ldc,
+                                                              int nsplit) {
+    __shared__ float red[8][32];
+    const long n = (long)N1 * N2, total = n + (colsum_out ? N1 : 0);
+    const int le = threadIdx.x & 31, grp = threadIdx.x >> 5;
+    const long i = (long)blockIdx.x * 32 + le;
+    float s = 0.f;
+    if (i < total) {
+        const float* p = i < n ? part + i : part + (long)nsplit * n + (i - n);
+        const long stride = i < n ? n : N1;
+        const int per = (nsplit + 7) / 8, k1 = min(nsplit, (grp + 1) * per);
+        int k = grp * per;
+        for (; k + 8 <= k1; k += 8) {
+            float v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[u] = p[(k + u) * stride];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += v[u];
+        }
+        for (; k < k1; ++k) s += p[k * stride];
+    }
+    red[grp][le] = s;
+    __syncthreads();
+    if (grp == 0 && i < total) {
+        float t = red[0][le];
+#pragma unroll
+        for (int g = 1; g < 8; ++g) t += red[g][le];
+        if (i < n) {
+            const long n1 = i / N2;
+            C[n1 * ldc + (i - n1 * N2)] += t;
+        } else {
+            colsum_out[i - n] += t;
+        }
     }
 }
 
@@ -1309,8 +1360,61 @@ static int tn_small_pass_rows(int M, long tiles) {
 }
 
 
+// Split plan of the 128 x 128 kernel (gemm_tn_kernel) for the shapes murcl_gemm_tn gives it: splits over M and the rows per split.
+static void tn_generic_plan(int M, int N1, int N2, int dtype, bool x3, int& splits, int& mps) {
+    const int rows = dtype == MURCL_DTYPE_BF16 ? 64 : 32;
+    const int t1 = (N1 + 127) / 128, t2 = (N2 + 127) / 128;
+    if (splits <= 0 && M <= 8 * rows && (long)N1 * N2 >= (1L << 20)) {
+        // bag-level layers: the whole reduction fits the four-slot ring (one memory round trip per workgroup), and every
+        // extra M-split would add N1*N2*4 bytes of float atomics (dW_ih: 6.3 MB each, ~5 us at the memory side)
+        splits = 1;
+    } else if (splits <= 0) {
+        // ONE workgroup per CU (then the four-slot ring: three slabs in flight), not two: measured per shape with
+        // tools/_tn128.py - dWa [262144 x 128]^T [. x 512] bf16 78 -> 67 us (64 splits instead of 128), DSMIL's dWq
+        // [131072 x 128]^T [. x 1024] 71 -> 63 us (32 instead of 64), the deferred head gradients [768 x 3072]^T [. x 512]
+        // f32 56 -> 40 us (3 instead of 8) and [. x 1024] 99 -> 62 us (2 instead of 8); the exact-f32 dWq [131072 x 128]^T [. x 1024] is MFMA-bound
+        // (313 against 289 us with two workgroups per CU: long f32 reductions keep the 512-workgroup target)
+        const int target = (dtype == MURCL_DTYPE_F32 && !x3 && M >= 16384) ? 2 * murcl_cu_budget() : murcl_cu_budget();
+        splits = (target + t1 * t2 - 1) / (t1 * t2);
+        if (splits >= 8) splits = ((splits + 7) / 8) * 8;                       // multiples of 8: the XCD-aware work map
+        if (murcl_cu_budget() < 256 && splits >= 8)                             // a reduced CU budget is a cap: round DOWN
+            while (splits > 8 && splits * t1 * t2 > target) splits -= 8;
+        while (splits > 8 && (long)(splits - 8) * rows * 4 >= M) splits -= 8;   // keep >= 4 slabs per split
+        while (splits > 1 && splits < 8 && (long)(splits - 1) * rows * 4 >= M) --splits;
+    }
+    mps = (M + splits - 1) / splits;
+    mps = ((mps + rows - 1) / rows) * rows;
+    if ((long)mps * (splits - 1) >= M) splits = (M + mps - 1) / mps;           // tiny M: drop empty splits
+}
+
+// The fixed-order split reduction is for the long patch-level reductions (the attention weight gradient: M = B*N rows); on
+// bag-level products the reduce launch costs more than the product ([768 x 3072]^T [. x 512] f32 38 -> 65 us, [4096 x 128]^T
+// [. x 512] bf16 9.3 -> 13.9 us), so they keep the atomics path.
+constexpr int TN_PARTS_MIN_M = 16384;
+
+// bytes of the split-partials workspace murcl_gemm_tn_ws takes for a shape that runs on the 128 x 128 kernel with more than
+// one split and at least TN_PARTS_MIN_M rows (0: nothing to reduce in a fixed order)
+extern "C" long murcl_gemm_tn_parts_bytes(int M, int N1, int N2, int dtype) {
+    if (M < TN_PARTS_MIN_M || N1 <= 0 || N2 <= 0) return 0;
+    const bool x3 = dtype == MURCL_DTYPE_F32X3;
+    if (x3) dtype = MURCL_DTYPE_F32;
+    if (dtype == MURCL_DTYPE_BF16 && N1 % 256 == 0 && N2 % 128 == 0 && M >= 4096) return 0;        // the wide kernel
+    if (dtype == MURCL_DTYPE_F32 && !x3 && M <= TS_MAXM) return 0;                                  // the single-writer small kernel
+    int splits = 0, mps = 0;
+    tn_generic_plan(M, N1, N2, dtype, x3, splits, mps);
+    return splits > 1 ? (long)splits * ((long)N1 * N2 + N1) * 4 : 0;
+}
+
+static int gemm_tn_launch(const void* A, const void* B, float* C, int M, int N1, int N2, int lda, int ldb, int ldc, int dtype,
+                          int splits, float* colsum_out, float* part, long part_bytes, hipStream_t stream);
+
 extern "C" int murcl_gemm_tn(const void* A, const void* B, float* C, int M, int N1, int N2, int lda, int ldb, int ldc,
                              int dtype, int splits, float* colsum_out, hipStream_t stream) {
+    return gemm_tn_launch(A, B, C, M, N1, N2, lda, ldb, ldc, dtype, splits, colsum_out, nullptr, 0, stream);
+}
+
+static int gemm_tn_launch(const void* A, const void* B, float* C, int M, int N1, int N2, int lda, int ldb, int ldc, int dtype,
+                          int splits, float* colsum_out, float* part, long part_bytes, hipStream_t stream) {
     if (M <= 0 || N1 <= 0 || N2 <= 0) return 0;
     const bool x3 = dtype == MURCL_DTYPE_F32X3;          // f32 storage, 3-term bf16 split on the bf16 matrix pipe (gemm_nt above)
     if (x3) dtype = MURCL_DTYPE_F32;
@@ -1354,27 +1458,13 @@ extern "C" int murcl_gemm_tn(const void* A, const void* B, float* C, int M, int 
     }
     const int rows = dtype == MURCL_DTYPE_BF16 ? 64 : 32;
     const int t1 = (N1 + 127) / 128, t2 = (N2 + 127) / 128;
-    if (splits <= 0 && M <= 8 * rows && (long)N1 * N2 >= (1L << 20)) {
-        // bag-level layers: the whole reduction fits the four-slot ring (one memory round trip per workgroup), and every
-        // extra M-split would add N1*N2*4 bytes of float atomics (dW_ih: 6.3 MB each, ~5 us at the memory side)
-        splits = 1;
-    } else if (splits <= 0) {
-        // ONE workgroup per CU (then the four-slot ring: three slabs in flight), not two: measured per shape with
-        // tools/_tn128.py - dWa [262144 x 128]^T [. x 512] bf16 78 -> 67 us (64 splits instead of 128), DSMIL's dWq
-        // [131072 x 128]^T [. x 1024] 71 -> 63 us (32 instead of 64), the deferred head gradients [768 x 3072]^T [. x 512]
-        // f32 56 -> 40 us (3 instead of 8) and [. x 1024] 99 -> 62 us (2 instead of 8); the exact-f32 dWq [131072 x 128]^T [. x 1024] is MFMA-bound
-        // (313 against 289 us with two workgroups per CU: long f32 reductions keep the 512-workgroup target)
-        const int target = (dtype == MURCL_DTYPE_F32 && !x3 && M >= 16384) ? 2 * murcl_cu_budget() : murcl_cu_budget();
-        splits = (target + t1 * t2 - 1) / (t1 * t2);
-        if (splits >= 8) splits = ((splits + 7) / 8) * 8;                       // multiples of 8: the XCD-aware work map
-        if (murcl_cu_budget() < 256 && splits >= 8)                             // a reduced CU budget is a cap: round DOWN
-            while (splits > 8 && splits * t1 * t2 > target) splits -= 8;
-        while (splits > 8 && (long)(splits - 8) * rows * 4 >= M) splits -= 8;   // keep >= 4 slabs per split
-        while (splits > 1 && splits < 8 && (long)(splits - 1) * rows * 4 >= M) --splits;
-    }
-    int mps = (M + splits - 1) / splits;
-    mps = ((mps + rows - 1) / rows) * rows;
-    if ((long)mps * (splits - 1) >= M) splits = (M + mps - 1) / mps;           // tiny M: drop empty splits
+    int mps = 0;
+    tn_generic_plan(M, N1, N2, dtype, x3, splits, mps);
+    // split partials through the caller's workspace (fixed-order sums) when it holds them all; float atomics into C otherwise.
+    // The reduce reads every split's tile, and a split without rows returns before storing one: the path needs every split to
+    // have rows (tn_generic_plan drops empty ones; checked here so that a later plan cannot feed it uninitialised memory)
+    if (M < TN_PARTS_MIN_M || splits <= 1 || !part || part_bytes < (long)splits * ((long)N1 * N2 + N1) * 4 || (long)mps * (splits - 1) >= M)
+        part = nullptr;
     dim3 grid(t1 * t2 * splits);
     const bool deep = (t1 * t2 * splits <= 256 || splits == 1) && mps > rows;   // small grid, several slabs per workgroup
 #define TN_LAUNCH(T, NS, X3)                                                                                        \
@@ -1383,7 +1473,7 @@ extern "C" int murcl_gemm_tn(const void* A, const void* B, float* C, int M, int 
         static MurclOncePerDevice once;                                                                                         \
         if (once.first()) { hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, NS * 32768); } \
         hipLaunchKernelGGL(k, grid, dim3(256), NS * 32768, stream, (const T*)A, (const T*)B, C, M, N1, N2, lda, ldb, ldc, mps, \
-                           splits, colsum_out);                                                                     \
+                           splits, colsum_out, part);                                                               \
     }
     if (dtype == MURCL_DTYPE_BF16) {
         if (deep) TN_LAUNCH(bf16_t, 4, false) else TN_LAUNCH(bf16_t, 2, false)
@@ -1395,6 +1485,13 @@ extern "C" int murcl_gemm_tn(const void* A, const void* B, float* C, int M, int 
         return -1;
     }
 #undef TN_LAUNCH
+    if (part) {
+        const int rc = MURCL_CHECK_LAUNCH();
+        if (rc) return rc;
+        const long n = (long)N1 * N2 + (colsum_out ? N1 : 0);
+        hipLaunchKernelGGL(tn_split_reduce_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, stream, part, C, colsum_out, N1, N2,
+                           ldc, splits);
+    }
     return MURCL_CHECK_LAUNCH();
 }
 
@@ -1453,7 +1550,7 @@ extern "C" int murcl_gemm_tn_ws(const void* A, const void* B, float* C, int M, i
             if (rc) return rc;
             colsum_out = nullptr;
         }
-        return murcl_gemm_tn(A, B, C, M, N1, N2, lda, ldb, ldc, dtype, splits, colsum_out, stream);
+        return gemm_tn_launch(A, B, C, M, N1, N2, lda, ldb, ldc, dtype, splits, colsum_out, ws, ws ? ws_bytes : 0, stream);
     }
     if (colsum_out && !colsum_part) {
         const int rc = murcl_colsum(A, colsum_out, M, N1, lda, dtype, 1, stream);

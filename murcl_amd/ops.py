@@ -360,10 +360,17 @@ def gemm_tn(A, B, *, splits=0, out=None, colsum_into=None, colsum_parts=None, x3
         colsum(colsum_parts[0].view(-1, N1)[:colsum_parts[1]], out=colsum_into, accumulate=True)
         colsum_into = None
     x3 = bool(x3) and A.dtype == torch.float32 and M >= 4096       # (``x3``: the 3-term bf16 split of gemm_nt, long f32 reductions)
+    # more than one M-split: the partial tiles go through a workspace and are added in a fixed order (run-to-run identical sums)
+    pb = _lib.lib().murcl_gemm_tn_parts_bytes(M, N1, N2, F32X3 if x3 else dt(A)) if splits <= 0 else 0
     with _span(lambda: (f"gemm_tn{'_wide' if wide else ''}<{'f32x3' if x3 else _DT_NAME[A.dtype]}>",
                dict(flops=2.0 * M * N1 * N2, bytes=M * (N1 + N2) * A.element_size() + N1 * N2 * 4))):
-        check(_lib.lib().murcl_gemm_tn(ptr(A), ptr(B), ptr(C), M, N1, N2, N1, N2, N2, F32X3 if x3 else dt(A), splits, ptr(colsum_into),
-                                       stream()), "gemm_tn")
+        if pb:
+            part = torch.empty((pb // 4,), dtype=torch.float32, device=A.device)
+            check(_lib.lib().murcl_gemm_tn_ws(ptr(A), ptr(B), ptr(C), M, N1, N2, N1, N2, N2, F32X3 if x3 else dt(A), splits,
+                                              ptr(colsum_into), ptr(part), pb, None, 0, stream()), "gemm_tn_ws")
+        else:
+            check(_lib.lib().murcl_gemm_tn(ptr(A), ptr(B), ptr(C), M, N1, N2, N1, N2, N2, F32X3 if x3 else dt(A), splits,
+                                           ptr(colsum_into), stream()), "gemm_tn")
     return C
 
 

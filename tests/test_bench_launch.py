@@ -88,7 +88,7 @@ def test_forced_distributed_run_carries_the_comm_block():
     of the z all-gather and of each gradient all-reduce, and the exposed (non-overlapped) part of a step."""
     env = dict(os.environ, MURCL_FORCE_DIST="1", MASTER_PORT="29533")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--stat-steps", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--full", "--stat-steps", "0",
                         "--no-cpu-baseline"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -105,7 +105,7 @@ def test_forced_distributed_run_carries_the_comm_block():
 def test_gpus_1_through_the_spawn_path_prints_the_contract_line():
     env = dict(os.environ, MURCL_BENCH_SPAWN="1")
     env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--full",
                         "--stat-steps", "0", "--no-cpu-baseline"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -142,3 +142,75 @@ def test_gpus_1_through_the_spawn_path_prints_the_contract_line():
     assert len(k2["avg_ms_each_untimed_pass"]) == 1 and k2["avg_launch_ms"] > 0
     assert k2["merge_launch"]["kernel"] == "abmil_pool_decoder" and k2["merge_launch"]["avg_ms_untimed_pass"] > 0
     assert "abmil_pool_combine" not in out["kernel_ms_per_step"] and "abmil_pool_decoder" in out["kernel_ms_per_step"]
+
+
+def test_parent_hands_the_ranks_an_absolute_dump_directory(monkeypatch, tmp_path):
+    """The ranks run from the repository root: a relative --dump-outputs is resolved against the caller's directory first."""
+    b = _bench()
+    calls = []
+    monkeypatch.setattr(b, "self_launch", lambda gpus, argv: calls.append(argv) or 0)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.chdir(tmp_path)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--dump-outputs", "out"])
+    with pytest.raises(SystemExit) as e:
+        b.main()
+    assert e.value.code == 0 and calls[0][-2:] == ["--dump-outputs", str(tmp_path / "out")]
+
+
+def test_breakdown_table_needs_the_full_run(monkeypatch, capsys):
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--breakdown"])
+    with pytest.raises(SystemExit) as e:
+        b.main()
+    assert e.value.code == 2 and "--breakdown needs --full" in capsys.readouterr().err
+
+
+def test_dumped_outputs_are_float32_files_within_the_limit(tmp_path):
+    """collect_outputs: the loss and every parameter by module prefix, as float32 host arrays; write_outputs: one .npy per array,
+    refusing more than 64 MB in all."""
+    import numpy as np
+    import torch
+    b = _bench()
+    torch.manual_seed(0)
+    lin, gru = torch.nn.Linear(4, 3), torch.nn.GRU(3, 5)
+    arrays = b.collect_outputs(torch.tensor(0.25, dtype=torch.float64), {"model": lin, "fc": gru.to(torch.bfloat16)})
+    assert sorted(arrays) == sorted(["loss", "model.weight", "model.bias"] + [f"fc.{k}" for k, _ in gru.named_parameters()])
+    b.write_outputs(str(tmp_path / "d"), arrays)
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "d" / f"{k}.npy")
+        assert got.dtype == np.float32 and got.shape == a.shape and np.array_equal(got, a), k
+    np.testing.assert_array_equal(np.load(tmp_path / "d" / "model.weight.npy"), lin.weight.detach().numpy())
+    with pytest.raises(RuntimeError, match="exceed the limit"):
+        b.write_outputs(str(tmp_path / "big"), {"x": np.zeros((b.DUMP_LIMIT_BYTES // 4 + 1,), np.float32)})
+    assert not (tmp_path / "big").exists()
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline (the K steps as hipGraph replays) and nothing measured beside it, and
+    --dump-outputs writes the loss and the updated parameters of the last timed step - bit for bit the same in a second run."""
+    import numpy as np
+    env = dict(os.environ)
+    env.pop("WORLD_SIZE", None)
+
+    def run(d):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                            "--dump-outputs", str(d)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    out = run(tmp_path / "out")
+    run(tmp_path / "again")
+    for f in os.listdir(tmp_path / "out"):
+        assert np.array_equal(np.load(tmp_path / "out" / f), np.load(tmp_path / "again" / f)), f
+    assert out["full"] is False and out["steps"] == 4 and out["warmup"] == 2 and out["n_gpus"] == 1
+    assert out["unit"] == "bags/s" and out["higher_is_better"] is True and out["dtype"] == "bf16" and out["value"] > 0
+    assert out["timing_mode"].startswith("hipgraph") and out["graph"]["replays"] * out["graph"]["steps_per_graph"] == 4
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 / 64 - 1) < 1e-3
+    for k in ("box", "roofline", "roofline_k2", "eager", "step_stats", "comm", "kernel_ms_per_step", "abmil_c2_f32", "m_full", "rows",
+              "cpu_baseline"):
+        assert k not in out, k
+    files = {f[:-4]: np.load(tmp_path / "out" / f) for f in os.listdir(tmp_path / "out")}
+    assert {"loss", "model.encoder.encoder.0.weight", "model.encoder.attention.0.weight", "fc.rnn.weight_ih_l0", "fc.fc.weight"} <= set(files)
+    assert all(a.dtype == np.float32 for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["model.encoder.encoder.0.weight"].shape == (512, 512) and np.isfinite(files["fc.rnn.weight_hh_l0"]).all()
+    assert abs(float(files["loss"]) - out["loss"]) <= 1e-6 + 1e-6 * abs(out["loss"])

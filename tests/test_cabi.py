@@ -70,6 +70,12 @@ def test_grouped_weight_gradient_plan_runs_on_host():
 
     one = L.murcl_gemm_tn_workspace_bytes(262144, 512, 512, _lib.BF16)
     assert one == 64 * 512 * 512 * 4
+    # the 128 x 128 kernel's split partials (the attention weight gradient [262144 x 128]^T [. x 512]): a whole number of
+    # [128 x 512] tiles + their column sums; one split, the wide kernel, the small f32 kernel and bag-level row counts need none
+    parts = L.murcl_gemm_tn_parts_bytes(262144, 128, 512, _lib.BF16)
+    assert parts > 0 and parts % ((128 * 512 + 128) * 4) == 0 and L.murcl_gemm_tn_workspace_bytes(262144, 128, 512, _lib.BF16) == 0
+    assert L.murcl_gemm_tn_parts_bytes(262144, 512, 512, _lib.BF16) == 0 and L.murcl_gemm_tn_parts_bytes(128, 512, 512, _lib.F32) == 0
+    assert L.murcl_gemm_tn_parts_bytes(768, 3072, 512, _lib.F32) == 0 and L.murcl_gemm_tn_parts_bytes(4096, 128, 512, _lib.BF16) == 0
     three = L.murcl_gemm_tn_grouped_workspace_bytes(probs(*[(262144, 512, 512)] * 3), 3, _lib.BF16)
     assert three == 3 * 21 * 512 * 512 * 4
     # unequal row counts: the longer product gets more splits; every split keeps >= 8 slabs of 32 rows

@@ -266,6 +266,37 @@ def test_gemm_tn_adds_the_bias_gradient_in_the_same_launch(dtype, M, N1, N2):
     _close(cs, pre.double() + A.double().sum(0), rtol=1e-4, atol=1e-4 * s if f32 else 1e-3 * s, msg="db")     # ADDED, not overwritten
 
 
+@pytest.mark.parametrize("dtype,M,N1,N2", [(torch.bfloat16, 262144, 128, 512), (torch.float32, 131072, 128, 1024), (torch.bfloat16, 16384, 128, 512)])
+def test_gemm_tn_split_sums_are_the_same_on_every_call(dtype, M, N1, N2):
+    """More than one M-split on the 128 x 128 kernel over >= 16384 rows (the attention weight gradient of the headline step:
+    [262144 x 128]^T [. x 512], 64 splits): the partial tiles meet in a fixed order, so repeated calls give bit-identical weight
+    and bias gradients."""
+    from murcl_amd import _lib, ops
+    dev = _dev()
+    assert _lib.lib().murcl_gemm_tn_parts_bytes(M, N1, N2, _lib.BF16 if dtype == torch.bfloat16 else _lib.F32) > 0
+    g = torch.Generator(device=dev).manual_seed(7)
+    A = torch.randn((M, N1), generator=g, device=dev).to(dtype)
+    B = torch.randn((M, N2), generator=g, device=dev).to(dtype)
+    runs = []
+    for _ in range(3):
+        cs = torch.zeros((N1,), device=dev)
+        runs.append((ops.gemm_tn(A, B, colsum_into=cs), cs))
+    for W, cs in runs[1:]:
+        assert torch.equal(W, runs[0][0]) and torch.equal(cs, runs[0][1])
+    _close(runs[0][0], A.double().t() @ B.double(), rtol=1e-4, atol=2e-2 * math.sqrt(M), msg="dW")
+    _close(runs[0][1], A.double().sum(0), rtol=1e-4, atol=1e-3 * math.sqrt(M), msg="db")
+
+
+def test_colsum_of_bag_level_rows_is_the_same_on_every_call():
+    """Bag-level column sums (the GRU bias gradient of the headline step: 128 rows x 3072) have one writer per column."""
+    from murcl_amd import ops
+    dev = _dev()
+    x = torch.randn((128, 3072), generator=torch.Generator(device=dev).manual_seed(3), device=dev)
+    outs = [ops.colsum(x) for _ in range(3)]
+    assert all(torch.equal(o, outs[0]) for o in outs[1:])
+    _close(outs[0], x.double().sum(0), rtol=1e-5, atol=1e-4, msg="colsum")
+
+
 @pytest.mark.parametrize("M,N1,N2", [(1, 4, 4), (15, 36, 100), (128, 1024, 128), (320, 2048, 512), (500, 60, 3072), (512, 512, 512),
                                      (513, 64, 64), (768, 3072, 512)])
 def test_gemm_tn_bag_level_f32_forms(M, N1, N2):

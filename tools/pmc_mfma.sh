@@ -8,8 +8,9 @@
 # Calibration: the same counters over tools/_abl/mfma_peak.hip (back-to-back v_mfma_f32_16x16x32_bf16, 2 waves per SIMD),
 # whose utilisation is 100 % by construction; per-kernel utilisation is reported raw and relative to it.
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1
-OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
+OUT=$ROOT/bench_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 -L > $OUT/counters_available.txt 2>&1
@@ -18,9 +19,9 @@ for c in SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU
   grep -qw "$c" $OUT/counters_available.txt && CNT="$CNT $c"
 done
 echo "counters: $CNT" > $OUT/mfma_pass.log
-hipcc --offload-arch=gfx950 -O3 -o $OUT/mfma_peak $GRAFT_REPO_ROOT/tools/_abl/mfma_peak.hip >> $OUT/mfma_pass.log 2>&1
+hipcc --offload-arch=gfx950 -O3 -o $OUT/mfma_peak $ROOT/tools/_abl/mfma_peak.hip >> $OUT/mfma_pass.log 2>&1
 rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d $OUT/mfma_cal -- $OUT/mfma_peak >> $OUT/mfma_pass.log 2>&1
-rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d $OUT/mfma -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --stat-steps 0 >> $OUT/mfma_pass.log 2>&1
+rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d $OUT/mfma -- python3 $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --stat-steps 0 >> $OUT/mfma_pass.log 2>&1
 python3 - <<PY
 import csv, glob, json, collections
 def collect(kind):
