@@ -12,7 +12,7 @@
  * caller passes torch.cuda.current_stream()); nothing allocates, frees or synchronises; workspaces
  * are caller-provided.  Return 0 on success, a hipError_t (>0) if a launch failed, <0 for
  * unsupported arguments.  dtype codes: 0 = f32, 1 = bf16 (f32 accumulate everywhere); murcl_gemm_nt
- * (dtype_in) and murcl_gemm_tn / murcl_gemm_tn_ws also take 2 = f32 tensors whose products run as a 3-term bf16 split on the bf16
+ * (dtype_in) and murcl_gemm_tn_grouped also take 2 = f32 tensors whose products run as a 3-term bf16 split on the bf16
  * matrix pipe (hi + mid + lo, six MFMAs per product, f32-level accuracy at 6/16 of the exact-f32 MFMA time).
  */
 #ifndef MURCL_AMD_H
@@ -43,36 +43,29 @@ int murcl_gemm_nt(const void* A, const void* B, void* C, int M, int N, int K, in
                   const float* rowscale, const float* rank1, int rows_per_bag, float* colsum_ws, int accumulate,
                   murcl_stream_t stream);
 
-/* C[N1,N2] (f32, pre-zeroed or accumulated into) += A[M,N1]^T . B[M,N2]: weight gradients, i.e. what
- * autograd's mm_backward computes for every Linear above; reduction over the patch dimension M is
- * split over `splits` workgroup groups (<=0: auto).  colsum_out (may be NULL) [N1] += column sums of A: the bias
- * gradient of the same layer, from the same pass over A (one more MFMA per fragment against a fragment of ones). */
-int murcl_gemm_tn(const void* A, const void* B, float* C, int M, int N1, int N2, int lda, int ldb, int ldc,
-                  int dtype, int splits, float* colsum_out, murcl_stream_t stream);
-/* The same with a caller-provided workspace (murcl_gemm_tn_workspace_bytes; 0 = this shape needs none): the big bf16
- * weight gradients (N1, N2 multiples of 256, M >= 16384) run on 256 x 256 tiles whose per-split partial sums go to the
- * workspace as plain stores and are added to C by a second launch - no float atomics; other shapes behave as murcl_gemm_tn. */
-long murcl_gemm_tn_workspace_bytes(int M, int N1, int N2, int dtype);
-/* Shapes with M >= 16384 rows that run on the 128 x 128 kernel with more than one M-split: given a workspace of at least
- * murcl_gemm_tn_parts_bytes (0 = one split or another kernel), murcl_gemm_tn_ws stores each split's partial tile there and adds
- * the splits to C (and colsum_out) in a fixed order by a second launch - the same result on every run. */
-long murcl_gemm_tn_parts_bytes(int M, int N1, int N2, int dtype);
-int murcl_gemm_tn_ws(const void* A, const void* B, float* C, int M, int N1, int N2, int lda, int ldb, int ldc, int dtype,
-                     int splits, float* colsum_out, float* ws, long ws_bytes, const float* colsum_part, int colsum_rows,
-                     murcl_stream_t stream);
-/* colsum_part (may be NULL) [colsum_rows][N1] f32: instead of the column sums of A, colsum_out += the sum of these rows -
- * the partial bias-gradient rows murcl_panel_gemm leaves in its colsum_ws when called without colsum_out - folded into the
- * launch that adds up the workspace (a small launch of its own on the other paths). */
-
-/* Several weight gradients C_g[N1_g,N2_g] += A_g[M_g,N1_g]^T . B_g[M_g,N2_g] as ONE launch of the square-tile kernel + ONE
- * reduce launch: the backward of the three encoder nn.Linear layers of abmil.py:12-21 (and of CLAM-SB's fc + gate pair,
- * clam.py:69-72), deferred until the last input gradient of the pass exists.  The (product, tile) pairs share one round of
- * workgroups (one per CU), so the per-launch fixed costs and the partial-tile traffic are paid once.  `probs` is a HOST array of
- * n <= 4 descriptors (f32 products of at most 512 rows each - bag-level / rollout-level layers - run as ONE launch of the 32 x 32
- * single-writer kernel instead, no workspace; of the flags they take MURCL_TN_OVERWRITE); colsum_part / colsum_rows / colsum_out as in murcl_gemm_tn_ws (colsum_out without colsum_part: column
- * sums of A_g by their own launch; not with flags).  flags / scale: applied by the reduce launch (grouped path only: a group with
- * flags that is not eligible returns -1).  Products the square-tile kernel does not take (see murcl_gemm_tn_ws), or a workspace below
- * murcl_gemm_tn_grouped_workspace_bytes (0 = the group is not eligible), run one by one through murcl_gemm_tn_ws. */
+/* Weight gradients C_g[N1_g,N2_g] (f32) += A_g[M_g,N1_g]^T . B_g[M_g,N2_g], g < n: what autograd's mm_backward computes for every
+ * Linear above.  `probs` is a HOST array of n >= 1 descriptors (lda / ldb / ldc in elements); colsum_out (may be NULL) [N1] += the
+ * column sums of A (the layer's bias gradient), or with colsum_part the sum of [colsum_rows][N1] f32 partial rows instead (what
+ * murcl_panel_gemm leaves in its colsum_ws when called without colsum_out).  dtype 0 / 1 / 2 (f32 tensors whose products run as a
+ * 3-term bf16 split on the bf16 matrix pipe).
+ *
+ * murcl_gemm_tn_plan (host only, no HIP call) writes the kernel form of every product into kinds[g] (may be NULL) and returns the
+ * workspace bytes murcl_gemm_tn_grouped wants for the same call (0: none), < 0 if the call is not supported.  The forms:
+ *   SMALL   f32, M <= 512: 32 x 32 single-writer tiles, the whole reduction in LDS, no atomics;
+ *   SQUARE  bf16, N1 and N2 multiples of 256, M >= 16384: 256 x 256 tiles split over the rows, partial tiles to the workspace and a
+ *           reduce launch that adds them to C (and the colsum_part rows to colsum_out) - no float atomics;
+ *   WIDE    bf16, N1 % 256 == 0, N2 % 128 == 0, M >= 4096, not SQUARE: 256 x 128 tiles, float atomics;
+ *   PARTS   the 128 x 128 kernel over more than one split of M >= 16384 rows: partial tiles to the workspace, added in a fixed order;
+ *   ATOMIC  the 128 x 128 kernel, splits added with float atomics;
+ *   EMPTY   M, N1 or N2 is 0: nothing runs.
+ * Up to MURCL_TN_MAXG products of kind SQUARE, or of kind SMALL without colsum_part, share ONE launch (the square tiles: one round
+ * of workgroups over all (product, tile, split) triples + one reduce launch - the encoder layers of abmil.py:12-21, CLAM-SB's fc +
+ * gate pair clam.py:69-72; the small tiles: the weight gradients of a PPO epoch, rlmil.py:179).  Any other call runs product by
+ * product, reusing one workspace.  flags apply where a launch writes C itself: SQUARE products (their reduce launch; colsum_out
+ * then only with colsum_part) and SMALL ones (MURCL_TN_OVERWRITE alone, without colsum_part); a flag on any other product makes
+ * the call unsupported.  Column sums that the chosen form cannot fold in run as launches of their own in front of it.
+ *
+ * murcl_gemm_tn_grouped runs exactly what murcl_gemm_tn_plan reports; a workspace below that is rejected (-1). */
 typedef struct murcl_tn_problem {
     const void* A; const void* B; float* C;
     const float* colsum_part; float* colsum_out;
@@ -85,7 +78,14 @@ typedef struct murcl_tn_problem {
                                  * murcl_panel_gemm epilogue 5: a-rows, b-rows, a-rows ...): row r of the product is written to row
                                  * ((r >> 4) & 1) * N1/2 + (r >> 5) * 16 + (r & 15) of C, i.e. C = [dWa; dWb] in natural order */
 #define MURCL_TN_SCALE 4
-long murcl_gemm_tn_grouped_workspace_bytes(const murcl_tn_problem* probs, int n, int dtype);
+#define MURCL_TN_KIND_EMPTY 0
+#define MURCL_TN_KIND_SMALL 1
+#define MURCL_TN_KIND_SQUARE 2
+#define MURCL_TN_KIND_PARTS 3
+#define MURCL_TN_KIND_ATOMIC 4
+#define MURCL_TN_KIND_WIDE 5
+#define MURCL_TN_MAXG 4
+long murcl_gemm_tn_plan(const murcl_tn_problem* probs, int n, int dtype, int* kinds);
 int murcl_gemm_tn_grouped(const murcl_tn_problem* probs, int n, int dtype, float* ws, long ws_bytes, murcl_stream_t stream);
 
 /* Weight-stationary bf16 variant of murcl_gemm_nt for the patch-level layers (M = bags*patches rows, K in
@@ -112,7 +112,7 @@ int murcl_gemm_tn_grouped(const murcl_tn_problem* probs, int n, int dtype, float
  * murcl_panel_gemm_supported tells whether a shape is covered (else use murcl_gemm_nt). */
 int murcl_panel_gemm_supported(int M, int N, int K, int epilogue, int rows_per_bag);
 /* colsum_ws given WITHOUT colsum_out: the partial rows stay in colsum_ws ([murcl_panel_gemm_colsum_rows][N] f32) and no second
- * launch runs; the caller adds them up (murcl_gemm_tn_ws's colsum_part: the weight gradient of the same layer comes next). */
+ * launch runs; the caller adds them up (murcl_tn_problem.colsum_part: the weight gradient of the same layer comes next). */
 int murcl_panel_gemm_colsum_rows(int M, int N, int K, int epilogue);
 int murcl_panel_gemm(const void* A, const void* W, void* C, int M, int N, int K, int epilogue, const float* bias,
                      void* bitmask_out, const void* bitmask_in, const float* rowscale, const float* rank1,
@@ -170,7 +170,7 @@ int murcl_abmil_pool_decoder(const float* part_ws, const float* Wd, const float*
  * (f32, ADDED to the buffers: per-workgroup partial rows in part_ws [512*(2D+1) floats] are summed by a second small
  * launch - 512 atomic adders per address cost a third of the kernel).  A_out (may be NULL) [B,N] receives the normalised
  * attention row softmax(s)/sqrt(N) the pass has in registers.  dH and dWa follow from dT through murcl_panel_gemm / murcl_gemm_nt
- * (MURCL_EPI_RANK1_MASK with rowscale = A, rank1 = dM) and murcl_gemm_tn. */
+ * (MURCL_EPI_RANK1_MASK with rowscale = A, rank1 = dM) and murcl_gemm_tn_grouped. */
 int murcl_abmil_pool_bwd(const void* H, const void* Wa, const float* ba, const float* wb, const float* scores,
                          const float* ml, const float* M, const float* dM, void* dT, float* dba, float* dwb,
                          float* dbb, float* part_ws, float* A_out, int B, int N, int L, int D, int dtype, int exact_tanh,

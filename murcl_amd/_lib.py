@@ -19,11 +19,7 @@ _P, _I, _L, _F = _c.c_void_p, _c.c_int, _c.c_long, _c.c_float
 
 SIGNATURES = {
     "murcl_gemm_nt": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _I, _P],
-    "murcl_gemm_tn": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
-    "murcl_gemm_tn_workspace_bytes": [_I, _I, _I, _I],
-    "murcl_gemm_tn_parts_bytes": [_I, _I, _I, _I],
-    "murcl_gemm_tn_ws": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _L, _P, _I, _P],
-    "murcl_gemm_tn_grouped_workspace_bytes": [_P, _I, _I],
+    "murcl_gemm_tn_plan": [_P, _I, _I, _P],
     "murcl_gemm_tn_grouped": [_P, _I, _I, _P, _L, _P],
     "murcl_panel_gemm_colsum_rows": [_I, _I, _I, _I],
     "murcl_panel_gemm_supported": [_I, _I, _I, _I, _I],
@@ -124,7 +120,7 @@ SIGNATURES = {
     "murcl_replay_tick": [_P, _P],
     "murcl_sgd_step": [_P, _P, _P, _L, _F, _F, _I, _F, _I, _I, _P],
 }
-_RESTYPE = {"murcl_ntxent_workspace_bytes": _L, "murcl_ntxent_xchg_bytes": _L, "murcl_kmeans_workspace_bytes": _L, "murcl_ppo_act_workspace": _L, "murcl_gemm_tn_workspace_bytes": _L, "murcl_gemm_tn_parts_bytes": _L, "murcl_gemm_tn_grouped_workspace_bytes": _L,
+_RESTYPE = {"murcl_ntxent_workspace_bytes": _L, "murcl_ntxent_xchg_bytes": _L, "murcl_kmeans_workspace_bytes": _L, "murcl_ppo_act_workspace": _L, "murcl_gemm_tn_plan": _L,
             "murcl_ppo_epoch_workspace": _L}
 
 
@@ -136,6 +132,8 @@ class TnProblem(ctypes.Structure):
 
 
 TN_OVERWRITE, TN_DEINTERLEAVE, TN_SCALE = 1, 2, 4
+TN_KIND_EMPTY, TN_KIND_SMALL, TN_KIND_SQUARE, TN_KIND_PARTS, TN_KIND_ATOMIC, TN_KIND_WIDE = 0, 1, 2, 3, 4, 5    # murcl_gemm_tn_plan
+TN_MAXG = 4
 
 
 _lib = None

@@ -1235,14 +1235,6 @@ static bool tn_group_plan(int n, const int* M, const int* N1, const int* N2, TnP
     }
     return true;
 }
-// bytes of workspace murcl_gemm_tn_ws wants for this shape (0: the shape takes the atomics path, no workspace needed)
-extern "C" long murcl_gemm_tn_workspace_bytes(int M, int N1, int N2, int dtype) {
-    if (!tn_sq_ok(M, N1, N2, N2, dtype)) return 0;
-    TnPlan pl;
-    if (!tn_group_plan(1, &M, &N1, &N2, &pl, nullptr)) return 0;
-    return pl.ws_floats * 4;
-}
-
 extern "C" int murcl_colsum(const void* x, float* out, int R, int N, int ld, int dtype, int accumulate, hipStream_t s);
 
 // Bag-level f32 weight gradients (M = a few hundred rows, outputs up to [3072 x 512]): C[N1,N2] += A[M,N1]^T B[M,N2].
@@ -1324,15 +1316,9 @@ __device__ __forceinline__ void tn_small_tile(const float* __restrict__ A, const
         if (do_cs && r16 == 0 && n1 < N1) colsum_out[n1] = overwrite ? accs[r] : colsum_out[n1] + accs[r];
     }
 }
-__global__ __launch_bounds__(256) void gemm_tn_small_f32_kernel(const float* __restrict__ A, const float* __restrict__ B,
-                                                                float* __restrict__ C, int M, int N1, int N2, int lda,
-                                                                int ldb, int ldc, float* __restrict__ colsum_out, int pass_rows) {
-    extern __shared__ __attribute__((aligned(16))) char ts_smem[];
-    tn_small_tile(A, B, C, M, N1, N2, lda, ldb, ldc, colsum_out, blockIdx.x, blockIdx.y, ts_smem, pass_rows);
-}
-// Up to four such products as ONE launch (the weight gradients of a PPO epoch, rlmil.py:179: four launches of 16 us whose
+// One to four such products as ONE launch (the weight gradients of a PPO epoch, rlmil.py:179: four launches of 16 us whose
 // tails and launch gaps add up): workgroup b belongs to the product g with tile0[g] <= b < tile0[g + 1]; its tile index
-// runs along N1 first, as the single-product grid does.
+// runs along N1 first.
 struct TnSmallGroup {
     const float* A[4]; const float* B[4]; float* C[4]; float* cs[4];
     int M[4], N1[4], N2[4], lda[4], ldb[4], ldc[4], tile0[5], pass_rows, overwrite[4];
@@ -1360,15 +1346,15 @@ static int tn_small_pass_rows(int M, long tiles) {
 }
 
 
-// Split plan of the 128 x 128 kernel (gemm_tn_kernel) for the shapes murcl_gemm_tn gives it: splits over M and the rows per split.
+// Split plan of the 128 x 128 kernel (gemm_tn_kernel): splits over M and the rows per split.
 static void tn_generic_plan(int M, int N1, int N2, int dtype, bool x3, int& splits, int& mps) {
     const int rows = dtype == MURCL_DTYPE_BF16 ? 64 : 32;
     const int t1 = (N1 + 127) / 128, t2 = (N2 + 127) / 128;
-    if (splits <= 0 && M <= 8 * rows && (long)N1 * N2 >= (1L << 20)) {
+    if (M <= 8 * rows && (long)N1 * N2 >= (1L << 20)) {
         // bag-level layers: the whole reduction fits the four-slot ring (one memory round trip per workgroup), and every
         // extra M-split would add N1*N2*4 bytes of float atomics (dW_ih: 6.3 MB each, ~5 us at the memory side)
         splits = 1;
-    } else if (splits <= 0) {
+    } else {
         // ONE workgroup per CU (then the four-slot ring: three slabs in flight), not two: measured per shape with
         // tools/_tn128.py - dWa [262144 x 128]^T [. x 512] bf16 78 -> 67 us (64 splits instead of 128), DSMIL's dWq
         // [131072 x 128]^T [. x 1024] 71 -> 63 us (32 instead of 64), the deferred head gradients [768 x 3072]^T [. x 512]
@@ -1391,115 +1377,126 @@ static void tn_generic_plan(int M, int N1, int N2, int dtype, bool x3, int& spli
 // bag-level products the reduce launch costs more than the product ([768 x 3072]^T [. x 512] f32 38 -> 65 us, [4096 x 128]^T
 // [. x 512] bf16 9.3 -> 13.9 us), so they keep the atomics path.
 constexpr int TN_PARTS_MIN_M = 16384;
+static_assert(TN_MAXG == MURCL_TN_MAXG, "include/murcl_amd.h");
 
-// bytes of the split-partials workspace murcl_gemm_tn_ws takes for a shape that runs on the 128 x 128 kernel with more than
-// one split and at least TN_PARTS_MIN_M rows (0: nothing to reduce in a fixed order)
-extern "C" long murcl_gemm_tn_parts_bytes(int M, int N1, int N2, int dtype) {
-    if (M < TN_PARTS_MIN_M || N1 <= 0 || N2 <= 0) return 0;
-    const bool x3 = dtype == MURCL_DTYPE_F32X3;
-    if (x3) dtype = MURCL_DTYPE_F32;
-    if (dtype == MURCL_DTYPE_BF16 && N1 % 256 == 0 && N2 % 128 == 0 && M >= 4096) return 0;        // the wide kernel
-    if (dtype == MURCL_DTYPE_F32 && !x3 && M <= TS_MAXM) return 0;                                  // the single-writer small kernel
-    int splits = 0, mps = 0;
-    tn_generic_plan(M, N1, N2, dtype, x3, splits, mps);
-    return splits > 1 ? (long)splits * ((long)N1 * N2 + N1) * 4 : 0;
-}
+// ------------------------------------------------------------------------------------- TN dispatch
+// ONE planner decides every product's kernel form; murcl_gemm_tn_plan reports it and murcl_gemm_tn_grouped runs it.
+typedef murcl_tn_problem TnProblem;     // include/murcl_amd.h
+struct TnStep { int kind, splits, mps; long ws_bytes; };
 
-static int gemm_tn_launch(const void* A, const void* B, float* C, int M, int N1, int N2, int lda, int ldb, int ldc, int dtype,
-                          int splits, float* colsum_out, float* part, long part_bytes, hipStream_t stream);
-
-extern "C" int murcl_gemm_tn(const void* A, const void* B, float* C, int M, int N1, int N2, int lda, int ldb, int ldc,
-                             int dtype, int splits, float* colsum_out, hipStream_t stream) {
-    return gemm_tn_launch(A, B, C, M, N1, N2, lda, ldb, ldc, dtype, splits, colsum_out, nullptr, 0, stream);
-}
-
-static int gemm_tn_launch(const void* A, const void* B, float* C, int M, int N1, int N2, int lda, int ldb, int ldc, int dtype,
-                          int splits, float* colsum_out, float* part, long part_bytes, hipStream_t stream) {
-    if (M <= 0 || N1 <= 0 || N2 <= 0) return 0;
+// How product p runs on its own: kernel form, M-splits, rows per split, workspace bytes.  -1: unsupported arguments, or flags the
+// form cannot apply (only the launches that write C themselves apply them).
+static int tn_plan_one(const TnProblem& p, int dtype, TnStep& st) {
+    st = TnStep{MURCL_TN_KIND_EMPTY, 0, 0, 0};
+    if (p.M <= 0 || p.N1 <= 0 || p.N2 <= 0) return p.flags ? -1 : 0;
+    if (p.colsum_part && (!p.colsum_out || p.colsum_rows <= 0 || p.N1 % 4)) return -1;
     const bool x3 = dtype == MURCL_DTYPE_F32X3;          // f32 storage, 3-term bf16 split on the bf16 matrix pipe (gemm_nt above)
-    if (x3) dtype = MURCL_DTYPE_F32;
-    const int es = dtype == MURCL_DTYPE_BF16 ? 2 : 4, epc = 16 / es;
-    if (N1 < epc || N2 < epc || N1 % epc || N2 % epc || (lda * es) % 16 || (ldb * es) % 16) return -1;
-    if (dtype == MURCL_DTYPE_BF16 && N1 % 256 == 0 && N2 % 128 == 0 && M >= 4096) {
-        const int tiles = (N1 / 256) * (N2 / 128);
-        int sp = splits;
-        if (sp <= 0) {                           // one 144 KiB-LDS workgroup per CU, splits % 8 == 0
-            sp = (256 + tiles - 1) / tiles;
-            sp = ((sp + 7) / 8) * 8;
-            while (sp > 8 && (long)(sp - 8) * 64 * 4 >= M) sp -= 8;                 // keep >= 4 slabs per split
-        }
-        int mps = (M + sp - 1) / sp;
+    const int base = x3 ? MURCL_DTYPE_F32 : dtype;
+    if (base != MURCL_DTYPE_F32 && base != MURCL_DTYPE_BF16) return -1;
+    const int es = base == MURCL_DTYPE_BF16 ? 2 : 4, epc = 16 / es;
+    if (p.N1 < epc || p.N2 < epc || p.N1 % epc || p.N2 % epc || (p.lda * es) % 16 || (p.ldb * es) % 16) return -1;
+    TnPlan pl;
+    if (tn_sq_ok(p.M, p.N1, p.N2, p.ldc, dtype) && tn_group_plan(1, &p.M, &p.N1, &p.N2, &pl, nullptr)) {
+        st = TnStep{MURCL_TN_KIND_SQUARE, pl.sp[0], pl.mps[0], pl.ws_floats * 4};
+        return p.flags && p.colsum_out && !p.colsum_part ? -1 : 0;   // flags: the reduce launch, which sums colsum_part rows only
+    }
+    if (dtype == MURCL_DTYPE_BF16 && p.N1 % 256 == 0 && p.N2 % 128 == 0 && p.M >= 4096) {
+        const int tiles = (p.N1 / 256) * (p.N2 / 128);
+        int sp = (256 + tiles - 1) / tiles;                // one 144 KiB-LDS workgroup per CU, splits % 8 == 0
+        sp = ((sp + 7) / 8) * 8;
+        while (sp > 8 && (long)(sp - 8) * 64 * 4 >= p.M) sp -= 8;                 // keep >= 4 slabs per split
+        int mps = (p.M + sp - 1) / sp;
         mps = ((mps + 63) / 64) * 64;
-        if ((long)mps * (sp - 1) >= M) sp = (M + mps - 1) / mps;
-        if (colsum_out) {                        // the wide kernel has no spare MFMA slots for the ones-trick: separate pass
-            const int rc = murcl_colsum(A, colsum_out, M, N1, lda, dtype, 1, stream);
-            if (rc) return rc;
-        }
-        auto k = gemm_tn_wide_kernel;
-        constexpr int LDS = 3 * 49152;
-        static MurclOncePerDevice once;      
-        if (once.first()) { hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); }
-        hipLaunchKernelGGL(k, dim3(tiles * sp), dim3(512), LDS, stream, (const bf16_t*)A, (const bf16_t*)B, C, M, N1, N2,
-                           lda, ldb, ldc, mps, sp);
-        return MURCL_CHECK_LAUNCH();
+        if ((long)mps * (sp - 1) >= p.M) sp = (p.M + mps - 1) / mps;
+        st = TnStep{MURCL_TN_KIND_WIDE, sp, mps, 0};
+        return p.flags ? -1 : 0;                           // float atomics into C: no flags
     }
     // one pass only: at M = 768 (the deferred head gradients of a T = 6 step) two serial passes per 32 x 32 tile take 78 us where
-    // the 128 x 128 ring kernel below takes 55 us ([768 x 3072 x 512], tools/tn_trace.sh); up to 512 rows the small tiles win
+    // the 128 x 128 ring kernel takes 55 us ([768 x 3072 x 512], tools/tn_trace.sh); up to 512 rows the small tiles win
     // (16.6 -> 12.2 us [128 x 3072 x 512], 7.7 -> 5.8 us [128 x 512 x 512], 23.7 -> 18.0 us [320 x 2048 x 512])
-    if (dtype == MURCL_DTYPE_F32 && !x3 && splits <= 0 && M <= TS_MAXM) {
-        const int pr = tn_small_pass_rows(M, (long)((N1 + TS_T - 1) / TS_T) * ((N2 + TS_T - 1) / TS_T));
-        const int mp = ((M < pr ? M : pr) + 15) & ~15;
-        static MurclOncePerDevice once;
-        if (once.first())
-            hipFuncSetAttribute((const void*)gemm_tn_small_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TS_MAXM * 128);
-        hipLaunchKernelGGL(gemm_tn_small_f32_kernel, dim3((N1 + TS_T - 1) / TS_T, (N2 + TS_T - 1) / TS_T), dim3(256), 2 * mp * 128,
-                           stream, (const float*)A, (const float*)B, C, M, N1, N2, lda, ldb, ldc, colsum_out, pr);
-        return MURCL_CHECK_LAUNCH();
+    if (dtype == MURCL_DTYPE_F32 && p.M <= TS_MAXM) {
+        st = TnStep{MURCL_TN_KIND_SMALL, 1, p.M, 0};
+        return (p.flags & ~MURCL_TN_OVERWRITE) || (p.flags && p.colsum_part) ? -1 : 0;    // the kernel writes C, applies no factor
     }
-    const int rows = dtype == MURCL_DTYPE_BF16 ? 64 : 32;
-    const int t1 = (N1 + 127) / 128, t2 = (N2 + 127) / 128;
-    int mps = 0;
-    tn_generic_plan(M, N1, N2, dtype, x3, splits, mps);
-    // split partials through the caller's workspace (fixed-order sums) when it holds them all; float atomics into C otherwise.
-    // The reduce reads every split's tile, and a split without rows returns before storing one: the path needs every split to
-    // have rows (tn_generic_plan drops empty ones; checked here so that a later plan cannot feed it uninitialised memory)
-    if (M < TN_PARTS_MIN_M || splits <= 1 || !part || part_bytes < (long)splits * ((long)N1 * N2 + N1) * 4 || (long)mps * (splits - 1) >= M)
-        part = nullptr;
-    dim3 grid(t1 * t2 * splits);
-    const bool deep = (t1 * t2 * splits <= 256 || splits == 1) && mps > rows;   // small grid, several slabs per workgroup
-#define TN_LAUNCH(T, NS, X3)                                                                                        \
-    {                                                                                                               \
-        auto k = gemm_tn_kernel<T, NS, X3>;                                                                         \
-        static MurclOncePerDevice once;                                                                                         \
-        if (once.first()) { hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, NS * 32768); } \
-        hipLaunchKernelGGL(k, grid, dim3(256), NS * 32768, stream, (const T*)A, (const T*)B, C, M, N1, N2, lda, ldb, ldc, mps, \
-                           splits, colsum_out, part);                                                               \
+    int splits, mps;
+    tn_generic_plan(p.M, p.N1, p.N2, base, x3, splits, mps);
+    // more than one split over many rows: partial tiles (+ their column sums) to the workspace, added in a fixed order.  The
+    // reduce reads every split's tile, and a split without rows stores none: every split must have rows
+    if (p.M >= TN_PARTS_MIN_M && splits > 1 && (long)mps * (splits - 1) < p.M)
+        st = TnStep{MURCL_TN_KIND_PARTS, splits, mps, (long)splits * ((long)p.N1 * p.N2 + p.N1) * 4};
+    else
+        st = TnStep{MURCL_TN_KIND_ATOMIC, splits, mps, 0};
+    return p.flags ? -1 : 0;
+}
+
+// How a call runs: every product on its own (TN_EACH), or all of them in one launch of the small-tile kernel or of the square-tile
+// kernel.  Fills kinds (may be NULL); returns the workspace bytes, -1 if unsupported.
+enum { TN_EACH, TN_SMALL_GROUP, TN_SQ_GROUP };
+static long tn_plan(const TnProblem* pr, int n, int dtype, int* kinds, int& form) {
+    form = TN_EACH;
+    bool small = n <= TN_MAXG, sq = n <= TN_MAXG;
+    long ws = 0;
+    int M[TN_MAXG], N1[TN_MAXG], N2[TN_MAXG];
+    for (int g = 0; g < n; ++g) {
+        TnStep st;
+        if (tn_plan_one(pr[g], dtype, st)) return -1;
+        if (kinds) kinds[g] = st.kind;
+        small = small && st.kind == MURCL_TN_KIND_SMALL && !pr[g].colsum_part;
+        sq = sq && st.kind == MURCL_TN_KIND_SQUARE;
+        ws = st.ws_bytes > ws ? st.ws_bytes : ws;
+        if (g < TN_MAXG) { M[g] = pr[g].M; N1[g] = pr[g].N1; N2[g] = pr[g].N2; }
     }
-    if (dtype == MURCL_DTYPE_BF16) {
-        if (deep) TN_LAUNCH(bf16_t, 4, false) else TN_LAUNCH(bf16_t, 2, false)
-    } else if (dtype == MURCL_DTYPE_F32 && x3) {
-        if (deep) TN_LAUNCH(float, 4, true) else TN_LAUNCH(float, 2, true)
-    } else if (dtype == MURCL_DTYPE_F32) {
-        if (deep) TN_LAUNCH(float, 4, false) else TN_LAUNCH(float, 2, false)
-    } else {
-        return -1;
+    if (n < 1) return 0;
+    if (small) form = TN_SMALL_GROUP;
+    TnPlan pl;
+    if (sq && tn_group_plan(n, M, N1, N2, &pl, nullptr)) {       // (every member fits a round alone: the group fits one round)
+        form = TN_SQ_GROUP;
+        ws = pl.ws_floats * 4;
     }
-#undef TN_LAUNCH
-    if (part) {
-        const int rc = MURCL_CHECK_LAUNCH();
-        if (rc) return rc;
-        const long n = (long)N1 * N2 + (colsum_out ? N1 : 0);
-        hipLaunchKernelGGL(tn_split_reduce_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, stream, part, C, colsum_out, N1, N2,
-                           ldc, splits);
+    return ws;                                     // one by one: one workspace, the largest a product needs
+}
+
+extern "C" long murcl_gemm_tn_plan(const TnProblem* pr, int n, int dtype, int* kinds) {
+    int form;
+    return tn_plan(pr, n, dtype, kinds, form);
+}
+
+// One launch of the small-tile kernel over n <= 4 SMALL products (C and colsum_out written with MURCL_TN_OVERWRITE, else added to).
+static int tn_small_launch(const TnProblem* pr, int n, hipStream_t stream) {
+    TnSmallGroup ga;
+    int tiles = 0, mmax = 0;
+    for (int g = 0; g < 4; ++g) {
+        const TnProblem& p = pr[g < n ? g : 0];
+        ga.A[g] = (const float*)p.A; ga.B[g] = (const float*)p.B; ga.C[g] = p.C; ga.cs[g] = p.colsum_out;
+        ga.M[g] = p.M; ga.N1[g] = p.N1; ga.N2[g] = p.N2; ga.lda[g] = p.lda; ga.ldb[g] = p.ldb; ga.ldc[g] = p.ldc;
+        ga.overwrite[g] = (p.flags & MURCL_TN_OVERWRITE) ? 1 : 0;
+        ga.tile0[g] = tiles;
+        if (g < n) {
+            tiles += ((p.N1 + TS_T - 1) / TS_T) * ((p.N2 + TS_T - 1) / TS_T);
+            if (p.M > mmax) mmax = p.M;
+        }
     }
+    for (int g = n; g < 5; ++g) ga.tile0[g] = tiles;                  // unused slots: empty ranges behind the last product
+    ga.pass_rows = tn_small_pass_rows(mmax, tiles);
+    const int mp = ((mmax < ga.pass_rows ? mmax : ga.pass_rows) + 15) & ~15;
+    static MurclOncePerDevice once;
+    if (once.first())
+        hipFuncSetAttribute((const void*)gemm_tn_small_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TS_MAXM * 128);
+    hipLaunchKernelGGL(gemm_tn_small_group_kernel, dim3(tiles), dim3(256), 2 * mp * 128, stream, ga);
     return MURCL_CHECK_LAUNCH();
 }
 
-// One launch of the grouped square-tile kernel + one reduce launch for n eligible products (tn_sq_ok, 16-byte aligned rows).
-typedef murcl_tn_problem TnProblem;     // include/murcl_amd.h
-static int tn_sq_launch(const TnProblem* pr, int n, float* ws, hipStream_t stream) {
+// One launch of the grouped square-tile kernel + one reduce launch for n <= 4 SQUARE products; column sums of A (colsum_out
+// without colsum_part) go first, by launches of their own.
+static int tn_sq_launch(const TnProblem* pr, int n, int dtype, float* ws, hipStream_t stream) {
     int M[TN_MAXG], N1[TN_MAXG], N2[TN_MAXG];
-    for (int g = 0; g < n; ++g) { M[g] = pr[g].M; N1[g] = pr[g].N1; N2[g] = pr[g].N2; }
+    for (int g = 0; g < n; ++g) {
+        M[g] = pr[g].M; N1[g] = pr[g].N1; N2[g] = pr[g].N2;
+        if (pr[g].colsum_out && !pr[g].colsum_part) {
+            const int rc = murcl_colsum(pr[g].A, pr[g].colsum_out, pr[g].M, pr[g].N1, pr[g].lda, dtype, 1, stream);
+            if (rc) return rc;
+        }
+    }
     TnPlan pl;
     TnGroupArgs ga;
     if (!tn_group_plan(n, M, N1, N2, &pl, ga.map)) return -1;
@@ -1511,7 +1508,8 @@ static int tn_sq_launch(const TnProblem* pr, int n, float* ws, hipStream_t strea
         ga.A[g] = (const bf16_t*)pr[h].A; ga.B[g] = (const bf16_t*)pr[h].B;
         ga.M[g] = pr[h].M; ga.N1[g] = pr[h].N1; ga.N2[g] = pr[h].N2; ga.lda[g] = pr[h].lda; ga.ldb[g] = pr[h].ldb;
         ga.mps[g] = pl.mps[h]; ga.part_off[g] = pl.part_off[h];
-        ra.C[g] = pr[h].C; ra.cs_part[g] = pr[h].colsum_part; ra.cs_out[g] = pr[h].colsum_out; ra.cs_rows[g] = pr[h].colsum_rows;
+        ra.C[g] = pr[h].C; ra.cs_part[g] = pr[h].colsum_part; ra.cs_out[g] = pr[h].colsum_part ? pr[h].colsum_out : nullptr;
+        ra.cs_rows[g] = pr[h].colsum_rows;
         ra.part_off[g] = pl.part_off[h]; ra.n4[g] = (long)pr[h].N1 * pr[h].N2 / 4; ra.nsplit[g] = pl.sp[h];
         ra.N1[g] = pr[h].N1; ra.N2[g] = pr[h].N2; ra.ldc[g] = pr[h].ldc; ra.flags[g] = pr[h].flags; ra.scale[g] = pr[h].scale;
         if (g < n) {
@@ -1530,111 +1528,77 @@ static int tn_sq_launch(const TnProblem* pr, int n, float* ws, hipStream_t strea
     hipLaunchKernelGGL(tn_reduce_kernel, dim3((unsigned)(blk + csb)), dim3(256), 0, stream, (const float*)ws, ra);
     return MURCL_CHECK_LAUNCH();
 }
-static bool tn_sq_problem_ok(const TnProblem& p, int dtype) {
-    return tn_sq_ok(p.M, p.N1, p.N2, p.ldc, dtype) && (p.lda * 2) % 16 == 0 && (p.ldb * 2) % 16 == 0 &&
-           (!p.colsum_part || (p.colsum_out && p.colsum_rows > 0));
-}
 
-// murcl_gemm_tn with a caller-provided workspace: the big bf16 weight gradients (N1, N2 multiples of 256, M >= 16384) run
-// on 256 x 256 tiles with the split partial sums stored to `ws` and added to C by a reduce launch (no float atomics);
-// every other shape, or a workspace that is too small, falls through to murcl_gemm_tn.
-extern "C" int murcl_gemm_tn_ws(const void* A, const void* B, float* C, int M, int N1, int N2, int lda, int ldb, int ldc,
-                                int dtype, int splits, float* colsum_out, float* ws, long ws_bytes, const float* colsum_part,
-                                int colsum_rows, hipStream_t stream) {
-    if (M <= 0 || N1 <= 0 || N2 <= 0) return 0;
-    if (colsum_part && (!colsum_out || colsum_rows <= 0 || N1 % 4)) return -1;
-    const long need = murcl_gemm_tn_workspace_bytes(M, N1, N2, dtype);
-    if (splits > 0 || !ws || !need || !tn_sq_ok(M, N1, N2, ldc, dtype) || (lda * 2) % 16 || (ldb * 2) % 16 || ws_bytes < need) {
-        if (colsum_part) {                      // the partial rows are added up by their own small launch
-            const int rc = murcl_colsum(colsum_part, colsum_out, colsum_rows, N1, N1, MURCL_DTYPE_F32, 1, stream);
-            if (rc) return rc;
-            colsum_out = nullptr;
-        }
-        return gemm_tn_launch(A, B, C, M, N1, N2, lda, ldb, ldc, dtype, splits, colsum_out, ws, ws ? ws_bytes : 0, stream);
-    }
-    if (colsum_out && !colsum_part) {
-        const int rc = murcl_colsum(A, colsum_out, M, N1, lda, dtype, 1, stream);
+// Product p on its own, as tn_plan_one planned it.  colsum_part rows that the form cannot fold in are added up by a launch in front.
+static int tn_launch_one(TnProblem p, int dtype, float* ws, hipStream_t stream) {
+    TnStep st;
+    tn_plan_one(p, dtype, st);
+    if (st.kind == MURCL_TN_KIND_EMPTY) return 0;
+    if (st.kind == MURCL_TN_KIND_SQUARE) return tn_sq_launch(&p, 1, dtype, ws, stream);
+    if (p.colsum_part) {
+        const int rc = murcl_colsum(p.colsum_part, p.colsum_out, p.colsum_rows, p.N1, p.N1, MURCL_DTYPE_F32, 1, stream);
         if (rc) return rc;
+        p.colsum_out = nullptr;
     }
-    const TnProblem p{A, B, C, colsum_part, colsum_part ? colsum_out : nullptr, M, N1, N2, lda, ldb, ldc, colsum_rows, 0, 1.f};
-    return tn_sq_launch(&p, 1, ws, stream);
-}
-
-// Several weight gradients C_g[N1_g,N2_g] += A_g[M_g,N1_g]^T B_g[M_g,N2_g] in ONE launch of the square-tile kernel + ONE reduce
-// launch (the three encoder layers of a backward pass: abmil.py:12-21; CLAM-SB's fc + gate pair: clam.py:69-72).  colsum_part /
-// colsum_rows / colsum_out per product as in murcl_gemm_tn_ws (colsum_out without colsum_part: the column sums of A_g by their
-// own launch).  Products the square-tile kernel does not take, or a workspace below murcl_gemm_tn_grouped_workspace_bytes, run one
-// by one through murcl_gemm_tn_ws with the same workspace.
-extern "C" long murcl_gemm_tn_grouped_workspace_bytes(const TnProblem* pr, int n, int dtype) {
-    if (n < 1 || n > TN_MAXG) return 0;
-    int M[TN_MAXG], N1[TN_MAXG], N2[TN_MAXG];
-    for (int g = 0; g < n; ++g) {
-        if (!tn_sq_problem_ok(pr[g], dtype)) return 0;
-        M[g] = pr[g].M; N1[g] = pr[g].N1; N2[g] = pr[g].N2;
-    }
-    TnPlan pl;
-    if (!tn_group_plan(n, M, N1, N2, &pl, nullptr)) return 0;
-    return pl.ws_floats * 4;
-}
-// f32 products of a few hundred rows each (the single-product path would take gemm_tn_small_f32_kernel for every one of them)
-static bool tn_small_group_ok(const TnProblem* pr, int n, int dtype) {
-    if (dtype != MURCL_DTYPE_F32 || n < 1 || n > 4) return false;
-    bool flagged = false;
-    for (int g = 0; g < n; ++g) flagged |= pr[g].flags != 0;
-    if (n == 1 && !flagged) return false;                      // a single plain product: murcl_gemm_tn's own dispatch
-    for (int g = 0; g < n; ++g) {
-        const TnProblem& p = pr[g];
-        if ((p.flags & ~MURCL_TN_OVERWRITE) || p.colsum_part || p.M <= 0 || p.M > TS_MAXM || p.N1 < 4 || p.N2 < 4 || p.N1 % 4 || p.N2 % 4 || p.lda % 4 || p.ldb % 4)
-            return false;
-    }
-    return true;
-}
-extern "C" int murcl_gemm_tn_grouped(const TnProblem* pr, int n, int dtype, float* ws, long ws_bytes, hipStream_t stream) {
-    if (n <= 0) return 0;
-    if (tn_small_group_ok(pr, n, dtype)) {
-        TnSmallGroup ga;
-        int tiles = 0, mmax = 0;
-        for (int g = 0; g < 4; ++g) {
-            const TnProblem& p = pr[g < n ? g : 0];
-            ga.A[g] = (const float*)p.A; ga.B[g] = (const float*)p.B; ga.C[g] = p.C; ga.cs[g] = p.colsum_out;
-            ga.M[g] = p.M; ga.N1[g] = p.N1; ga.N2[g] = p.N2; ga.lda[g] = p.lda; ga.ldb[g] = p.ldb; ga.ldc[g] = p.ldc;
-            ga.overwrite[g] = (p.flags & MURCL_TN_OVERWRITE) ? 1 : 0;
-            ga.tile0[g] = tiles;
-            if (g < n) {
-                tiles += ((p.N1 + TS_T - 1) / TS_T) * ((p.N2 + TS_T - 1) / TS_T);
-                if (p.M > mmax) mmax = p.M;
-            }
+    if (st.kind == MURCL_TN_KIND_SMALL) return tn_small_launch(&p, 1, stream);
+    const void *A = p.A, *B = p.B;
+    float *C = p.C, *colsum_out = p.colsum_out;
+    const int M = p.M, N1 = p.N1, N2 = p.N2, lda = p.lda, ldb = p.ldb, ldc = p.ldc, splits = st.splits, mps = st.mps;
+    if (st.kind == MURCL_TN_KIND_WIDE) {
+        if (colsum_out) {                        // the wide kernel has no spare MFMA slots for the ones-trick: separate pass
+            const int rc = murcl_colsum(A, colsum_out, M, N1, lda, dtype, 1, stream);
+            if (rc) return rc;
         }
-        for (int g = n; g < 5; ++g) ga.tile0[g] = tiles;                  // unused slots: empty ranges behind the last product
-        ga.pass_rows = tn_small_pass_rows(mmax, tiles);
-        const int mp = ((mmax < ga.pass_rows ? mmax : ga.pass_rows) + 15) & ~15;
+        auto k = gemm_tn_wide_kernel;
+        constexpr int LDS = 3 * 49152;
         static MurclOncePerDevice once;
-        if (once.first())
-            hipFuncSetAttribute((const void*)gemm_tn_small_group_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * TS_MAXM * 128);
-        hipLaunchKernelGGL(gemm_tn_small_group_kernel, dim3(tiles), dim3(256), 2 * mp * 128, stream, ga);
+        if (once.first()) { hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS); }
+        hipLaunchKernelGGL(k, dim3((N1 / 256) * (N2 / 128) * splits), dim3(512), LDS, stream, (const bf16_t*)A, (const bf16_t*)B, C,
+                           M, N1, N2, lda, ldb, ldc, mps, splits);
         return MURCL_CHECK_LAUNCH();
     }
-    const long need = (n <= TN_MAXG) ? murcl_gemm_tn_grouped_workspace_bytes(pr, n, dtype) : 0;
-    if (!need || !ws || ws_bytes < need) {
-        for (int g = 0; g < n; ++g)
-            if (pr[g].flags) return -1;                 // overwrite / de-interleave / scale live in the grouped reduce launch only
-        for (int g = 0; g < n; ++g) {
-            const TnProblem& p = pr[g];
-            const int rc = murcl_gemm_tn_ws(p.A, p.B, p.C, p.M, p.N1, p.N2, p.lda, p.ldb, p.ldc, dtype, 0, p.colsum_out, ws, ws_bytes,
-                                            p.colsum_part, p.colsum_rows, stream);
-            if (rc) return rc;
-        }
-        return 0;
+    // PARTS / ATOMIC: the 128 x 128 kernel
+    const bool x3 = dtype == MURCL_DTYPE_F32X3;
+    float* part = st.kind == MURCL_TN_KIND_PARTS ? ws : nullptr;
+    const int rows = dtype == MURCL_DTYPE_BF16 ? 64 : 32;
+    const int t1 = (N1 + 127) / 128, t2 = (N2 + 127) / 128;
+    dim3 grid(t1 * t2 * splits);
+    const bool deep = (t1 * t2 * splits <= 256 || splits == 1) && mps > rows;   // small grid, several slabs per workgroup
+#define TN_LAUNCH(T, NS, X3)                                                                                        \
+    {                                                                                                               \
+        auto k = gemm_tn_kernel<T, NS, X3>;                                                                         \
+        static MurclOncePerDevice once;                                                                                         \
+        if (once.first()) { hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, NS * 32768); } \
+        hipLaunchKernelGGL(k, grid, dim3(256), NS * 32768, stream, (const T*)A, (const T*)B, C, M, N1, N2, lda, ldb, ldc, mps, \
+                           splits, colsum_out, part);                                                               \
     }
-    TnProblem q[TN_MAXG];
+    if (dtype == MURCL_DTYPE_BF16) {
+        if (deep) TN_LAUNCH(bf16_t, 4, false) else TN_LAUNCH(bf16_t, 2, false)
+    } else if (x3) {
+        if (deep) TN_LAUNCH(float, 4, true) else TN_LAUNCH(float, 2, true)
+    } else {
+        if (deep) TN_LAUNCH(float, 4, false) else TN_LAUNCH(float, 2, false)
+    }
+#undef TN_LAUNCH
+    if (part) {
+        const int rc = MURCL_CHECK_LAUNCH();
+        if (rc) return rc;
+        const long n = (long)N1 * N2 + (colsum_out ? N1 : 0);
+        hipLaunchKernelGGL(tn_split_reduce_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, stream, part, C, colsum_out, N1, N2,
+                           ldc, splits);
+    }
+    return MURCL_CHECK_LAUNCH();
+}
+
+extern "C" int murcl_gemm_tn_grouped(const TnProblem* pr, int n, int dtype, float* ws, long ws_bytes, hipStream_t stream) {
+    int form;
+    const long need = tn_plan(pr, n, dtype, nullptr, form);
+    if (need < 0 || (need > 0 && (!ws || ws_bytes < need))) return -1;
+    if (form == TN_SMALL_GROUP) return tn_small_launch(pr, n, stream);
+    if (form == TN_SQ_GROUP) return tn_sq_launch(pr, n, dtype, ws, stream);
     for (int g = 0; g < n; ++g) {
-        q[g] = pr[g];
-        if (q[g].flags && ((q[g].colsum_out && !q[g].colsum_part) || ((q[g].flags & MURCL_TN_DEINTERLEAVE) && q[g].N1 % 32))) return -1;
-        if (q[g].colsum_out && !q[g].colsum_part) {
-            const int rc = murcl_colsum(q[g].A, q[g].colsum_out, q[g].M, q[g].N1, q[g].lda, dtype, 1, stream);
-            if (rc) return rc;
-            q[g].colsum_out = nullptr;
-        }
+        const int rc = tn_launch_one(pr[g], dtype, ws, stream);
+        if (rc) return rc;
     }
-    return tn_sq_launch(q, n, ws, stream);
+    return 0;
 }

@@ -292,31 +292,88 @@ def relu_bitmask(x):
     return bits
 
 
-import os as _os
-_TN_SQ = True             # test hook: False keeps the 256 x 128 atomics kernel (the form shapes without a workspace take)
+_TN_NAME = {_lib.TN_KIND_SQUARE: "gemm_tn_sq", _lib.TN_KIND_WIDE: "gemm_tn_wide"}       # timer keys; other kinds: gemm_tn
+_CODE_NAME = {F32: "f32", BF16: "bf16", F32X3: "f32x3"}
+
+
+def gemm_tn_plan(problems, code):
+    """murcl_gemm_tn_plan for ``problems`` = [(A, B, out, colsum_into, colsum_parts, opts)] (contiguous 2-D operands of one dtype)
+    -> (descriptor array without outputs, workspace bytes or < 0 if unsupported, kinds)."""
+    n = len(problems)
+    arr, kinds = (_lib.TnProblem * n)(), (ctypes.c_int * n)()
+    for g, (A, B, _, ci, cp, opts) in enumerate(problems):
+        assert A.dtype == B.dtype == problems[0][0].dtype and A.shape[0] == B.shape[0]
+        (M, N1), N2 = A.shape, B.shape[1]
+        flags, scale = 0, 1.0
+        if opts and opts.get("scale") is not None:
+            flags, scale = flags | _lib.TN_SCALE, float(opts["scale"])
+        if opts and opts.get("deinterleave"):
+            flags |= _lib.TN_DEINTERLEAVE
+        if opts and opts.get("overwrite"):
+            flags |= _lib.TN_OVERWRITE
+        assert ci is None or (ci.dtype == torch.float32 and ci.is_contiguous() and ci.numel() == N1)
+        arr[g] = _lib.TnProblem(ptr(A), ptr(B), None, ptr(cp[0]) if cp else None, ptr(ci), M, N1, N2, N1, N2, N2, cp[1] if cp else 0,
+                                flags, scale)
+    return arr, _lib.lib().murcl_gemm_tn_plan(arr, n, code, kinds), list(kinds)
+
+
+def _tn_sq_group(kinds):
+    """The grouped square-tile form: 2 to MURCL_TN_MAXG products of the square-tile kind share one launch."""
+    return 1 < len(kinds) <= _lib.TN_MAXG and all(k == _lib.TN_KIND_SQUARE for k in kinds)
+
+
+def _tn_run(problems, code, plan, write):
+    """Runs ``problems`` as planned by ``gemm_tn_plan`` in ONE murcl_gemm_tn_grouped call.  A product without ``out`` gets a fresh output:
+    WRITTEN by the kernel (no zero-fill launch; so is its ``colsum_into``) where ``write(kind, problem)`` says so, zeros to add into
+    otherwise.  The timer span is named from the kinds.  -> list of C"""
+    arr, wsb, kinds = plan
+    if wsb < 0:
+        raise RuntimeError(f"murcl_amd: murcl_gemm_tn_plan rejects {[(tuple(p[0].shape), tuple(p[1].shape)) for p in problems]} ({wsb})")
+    Cs, written = [], False
+    for g, (A, B, out, *_) in enumerate(problems):
+        N1, N2 = A.shape[1], B.shape[1]
+        if out is None:
+            written = write(kinds[g], problems[g])
+            out = (torch.empty if written else torch.zeros)((N1, N2), dtype=torch.float32, device=A.device)
+            if written:
+                arr[g].flags |= _lib.TN_OVERWRITE
+        assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (N1, N2)
+        arr[g].C = ptr(out)
+        Cs.append(out)
+    ws = torch.empty((wsb // 4,), dtype=torch.float32, device=Cs[0].device) if wsb else None
+    if _tn_sq_group(kinds):
+        key = f"gemm_tn_sq_grouped{len(kinds)}<bf16>"
+    elif all(k == _lib.TN_KIND_SMALL for k in kinds) and (len(kinds) > 1 or written):
+        key = None                                             # bag-level groups and fresh bag-level products: not timed
+    else:
+        key = "+".join(sorted({_TN_NAME.get(k, "gemm_tn") for k in kinds})) + f"<{_CODE_NAME[code]}>"
+    span = _span(lambda: (key, dict(flops=sum(2.0 * p[0].shape[0] * p[0].shape[1] * p[1].shape[1] for p in problems),
+                                    bytes=sum(p[0].shape[0] * (p[0].shape[1] + p[1].shape[1]) * p[0].element_size()
+                                              + p[0].shape[1] * p[1].shape[1] * 4 for p in problems)))) if key else _NULL
+    with span:
+        check(_lib.lib().murcl_gemm_tn_grouped(arr, len(problems), code, ptr(ws), wsb, stream()), "gemm_tn_grouped")
+    return Cs
 
 
 def gemm_tn_with_colsum(A, B):
-    """(A^T B, column sums of A) for a fresh bag-level f32 gradient pair - a Linear's (dW, db) from (dy, x) - in ONE launch where the
-    single-writer 32 x 32 kernel takes the shape (its workgroups of the first column tile form the sums with one more MFMA per
-    step), else as ``gemm_tn`` + ``colsum``."""
+    """(A^T B, column sums of A) for a fresh gradient pair - a Linear's (dW, db) from (dy, x) - in ONE launch where the single-writer
+    32 x 32 kernel takes the shape (its workgroups of the first column tile form the sums with one more MFMA per step), else as
+    ``gemm_tn`` + ``colsum``."""
     _need_cuda(A, B)
     A, B = _c(A), _c(B)
-    M, N1 = A.shape
-    N2 = B.shape[1]
-    if A.dtype == torch.float32 and B.dtype == torch.float32 and M <= 512 and _TN_SMALL_GROUP and N1 % 4 == 0 and N2 % 4 == 0:
-        C = torch.empty((N1, N2), dtype=torch.float32, device=A.device)
-        cs = torch.empty((N1,), dtype=torch.float32, device=A.device)
-        arr = (_lib.TnProblem * 1)(_lib.TnProblem(ptr(A), ptr(B), ptr(C), None, ptr(cs), M, N1, N2, N1, N2, N2, 0, _lib.TN_OVERWRITE, 1.0))
-        if _lib.lib().murcl_gemm_tn_grouped(arr, 1, F32, None, 0, stream()) == 0:
-            return C, cs
-    return gemm_tn(A, B), colsum(A)
+    cs = torch.empty((A.shape[1],), dtype=torch.float32, device=A.device)
+    probs = [(A, B, None, cs, None, None)]
+    plan = gemm_tn_plan(probs, dt(A))
+    if plan[1] < 0 or plan[2][0] != _lib.TN_KIND_SMALL:
+        return gemm_tn(A, B), colsum(A)
+    return _tn_run(probs, dt(A), plan, lambda k, p: True)[0], cs
 
 
-def gemm_tn(A, B, *, splits=0, out=None, colsum_into=None, colsum_parts=None, x3=False):
+def gemm_tn(A, B, *, out=None, colsum_into=None, colsum_parts=None, x3=False):
     """C[N1,N2] (f32) = A[M,N1]^T @ B[M,N2]  (adds into ``out`` when given).  ``colsum_into`` [N1] f32: the column sums
     of A are ADDED to it in the same launch (the bias gradient that goes with this weight gradient); with
-    ``colsum_parts`` = (rows [R,N1] f32, R) from ``panel_gemm(colsum_defer=True)`` those rows are summed instead."""
+    ``colsum_parts`` = (rows [R,N1] f32, R) from ``panel_gemm(colsum_defer=True)`` those rows are summed instead.  ``x3``: the
+    3-term bf16 split of gemm_nt for long f32 reductions."""
     _need_cuda(A, B)
     A, B = _c(A), _c(B)
     M, N1 = A.shape
@@ -326,7 +383,7 @@ def gemm_tn(A, B, *, splits=0, out=None, colsum_into=None, colsum_parts=None, x3
     if colsum_parts is not None and (colsum_into is None or N1 % 4):
         raise ValueError("colsum_parts needs colsum_into and N1 % 4 == 0")
     if N1 % epc:                    # tiny head gradients (N1 = 1, 2, 10): zero-pad the columns of A, slice the result
-        res = gemm_tn(pad_cols(A, ((N1 + epc - 1) // epc) * epc), B, splits=splits)[:N1]      # (the first N1 rows: contiguous)
+        res = gemm_tn(pad_cols(A, ((N1 + epc - 1) // epc) * epc), B)[:N1]      # (the first N1 rows: contiguous)
         if colsum_into is not None:
             colsum(A, out=colsum_into, accumulate=True)
         if out is None:
@@ -334,144 +391,39 @@ def gemm_tn(A, B, *, splits=0, out=None, colsum_into=None, colsum_parts=None, x3
         if out.is_contiguous() and out.dtype == torch.float32:
             return axpby(out, res, 1.0, 1.0, out=out)
         return out.add_(res)
-    if colsum_into is not None:
-        assert colsum_into.dtype == torch.float32 and colsum_into.is_contiguous() and colsum_into.numel() == N1
-    if (out is None and colsum_into is None and A.dtype == torch.float32 and M <= 512 and splits <= 0 and not x3 and _TN_SMALL_GROUP
-            and N2 % 4 == 0):
-        # a fresh bag-level gradient: the single-writer 32 x 32 kernel WRITES it (no zero-fill launch in front, no read of C)
-        C = torch.empty((N1, N2), dtype=torch.float32, device=A.device)
-        arr = (_lib.TnProblem * 1)(_lib.TnProblem(ptr(A), ptr(B), ptr(C), None, None, M, N1, N2, N1, N2, N2, 0, _lib.TN_OVERWRITE, 1.0))
-        if _lib.lib().murcl_gemm_tn_grouped(arr, 1, F32, None, 0, stream()) == 0:
-            return C
-        # (the library declines flagged products when its small-tile kernel is switched off, MURCL_TN_SMALL=0: zero-fill + the
-        #  accumulating entry point below)
-    C = out if out is not None else torch.zeros((N1, N2), dtype=torch.float32, device=A.device)
-    wide = A.dtype == torch.bfloat16 and N1 % 256 == 0 and N2 % 128 == 0 and M >= 4096     # murcl_gemm_tn's dispatch
-    wsb = _lib.lib().murcl_gemm_tn_workspace_bytes(M, N1, N2, dt(A)) if (splits <= 0 and _TN_SQ) else 0
-    if wsb:         # 256 x 256 tiles, partial sums through a workspace + reduce launch (no float atomics)
-        ws = torch.empty((wsb // 4,), dtype=torch.float32, device=A.device)
-        with _span(lambda: (f"gemm_tn_sq<{_DT_NAME[A.dtype]}>",
-                   dict(flops=2.0 * M * N1 * N2, bytes=M * (N1 + N2) * A.element_size() + N1 * N2 * 4))):
-            check(_lib.lib().murcl_gemm_tn_ws(ptr(A), ptr(B), ptr(C), M, N1, N2, N1, N2, N2, dt(A), splits, ptr(colsum_into),
-                                              ptr(ws), wsb, ptr(colsum_parts[0]) if colsum_parts else None,
-                                              colsum_parts[1] if colsum_parts else 0, stream()), "gemm_tn_ws")
-        return C
-    if colsum_parts is not None:                      # other paths: the partial rows get their own small launch
-        colsum(colsum_parts[0].view(-1, N1)[:colsum_parts[1]], out=colsum_into, accumulate=True)
-        colsum_into = None
-    x3 = bool(x3) and A.dtype == torch.float32 and M >= 4096       # (``x3``: the 3-term bf16 split of gemm_nt, long f32 reductions)
-    # more than one M-split: the partial tiles go through a workspace and are added in a fixed order (run-to-run identical sums)
-    pb = _lib.lib().murcl_gemm_tn_parts_bytes(M, N1, N2, F32X3 if x3 else dt(A)) if splits <= 0 else 0
-    with _span(lambda: (f"gemm_tn{'_wide' if wide else ''}<{'f32x3' if x3 else _DT_NAME[A.dtype]}>",
-               dict(flops=2.0 * M * N1 * N2, bytes=M * (N1 + N2) * A.element_size() + N1 * N2 * 4))):
-        if pb:
-            part = torch.empty((pb // 4,), dtype=torch.float32, device=A.device)
-            check(_lib.lib().murcl_gemm_tn_ws(ptr(A), ptr(B), ptr(C), M, N1, N2, N1, N2, N2, F32X3 if x3 else dt(A), splits,
-                                              ptr(colsum_into), ptr(part), pb, None, 0, stream()), "gemm_tn_ws")
-        else:
-            check(_lib.lib().murcl_gemm_tn(ptr(A), ptr(B), ptr(C), M, N1, N2, N1, N2, N2, F32X3 if x3 else dt(A), splits,
-                                           ptr(colsum_into), stream()), "gemm_tn")
-    return C
+    # a fresh bag-level gradient: the single-writer 32 x 32 kernel WRITES it (no zero-fill launch in front, no read of C)
+    fresh = out is None and colsum_into is None and not x3
+    code = F32X3 if (x3 and A.dtype == torch.float32 and M >= 4096) else dt(A)
+    probs = [(A, B, out, colsum_into, colsum_parts, None)]
+    return _tn_run(probs, code, gemm_tn_plan(probs, code), lambda k, p: fresh and k == _lib.TN_KIND_SMALL)[0]
 
 
 def gemm_tn_grouped(problems, fresh=False):
-    """Several weight gradients in ONE launch (+ one reduce launch): ``problems`` = list of (A [M,N1], B [M,N2], out or None,
-    colsum_into or None, colsum_parts or None[, opts]) with the meanings of ``gemm_tn``; returns the list of C tensors.  bf16 products
-    with N1, N2 multiples of 256 and M >= 16384 share one round of workgroups (murcl_gemm_tn_grouped); anything else, or more
-    than four products, runs through ``gemm_tn`` one by one.  ``opts`` (dict, grouped path only - check ``gemm_tn_grouped_ok``):
-    ``scale`` (product and column sums times a factor), ``deinterleave`` (rows arrive as alternating 16-row blocks of two halves: C
-    = [first half; second half] in natural order).  ``fresh``: products without ``out`` / column sums into a fresh tensor are WRITTEN
-    by the reduce launch (no zero-fill launch before it)."""
-    problems = [tuple(p) + (None,) * (6 - len(p)) for p in problems]
-    if gemm_tn_small_grouped_ok(problems):
-        n = len(problems)
-        arr = (_lib.TnProblem * n)()
-        keep, Cs = [], []
-        for g, (A, B, out, ci, _, _) in enumerate(problems):
-            _need_cuda(A, B)
-            A, B = _c(A), _c(B)
-            (M, N1), N2 = A.shape, B.shape[1]
-            write = out is None and ci is None                 # a fresh product is written, not added to zeros
-            C = out if out is not None else (torch.empty if write else torch.zeros)((N1, N2), dtype=torch.float32, device=A.device)
-            assert C.dtype == torch.float32 and C.is_contiguous() and tuple(C.shape) == (N1, N2)
-            assert ci is None or (ci.dtype == torch.float32 and ci.is_contiguous() and ci.numel() == N1)
-            keep.append((A, B))
-            Cs.append(C)
-            arr[g] = _lib.TnProblem(ptr(A), ptr(B), ptr(C), None, ptr(ci), M, N1, N2, N1, N2, N2, 0, _lib.TN_OVERWRITE if write else 0, 1.0)
-        if _lib.lib().murcl_gemm_tn_grouped(arr, n, F32, None, 0, stream()) == 0:
-            return Cs
-        # (declined: the library's small-tile kernel is switched off, MURCL_TN_SMALL=0 - one product at a time below)
-        return [gemm_tn(A, B, out=out, colsum_into=ci) for A, B, out, ci, _, _ in problems]
-    if not gemm_tn_grouped_ok(problems):
-        assert all(p[5] is None for p in problems), "scale / deinterleave need the grouped launch (gemm_tn_grouped_ok)"
+    """Several weight gradients through ONE murcl_gemm_tn_grouped call: ``problems`` = list of (A [M,N1], B [M,N2], out or None,
+    colsum_into or None, colsum_parts or None[, opts]) with the meanings of ``gemm_tn``; returns the list of C tensors.  2-4 bf16
+    products of the square-tile kind share one round of workgroups and one reduce launch (``gemm_tn_grouped_ok``), 2-4 bag-level f32
+    products one launch of the 32 x 32-tile kernel; anything else runs one product at a time.  ``opts`` (dict, the
+    grouped square-tile launch only): ``scale`` (product and column sums times a factor), ``deinterleave`` (rows arrive as alternating
+    16-row blocks of two halves: C = [first half; second half] in natural order), ``overwrite``.  ``fresh``: products of that launch
+    without ``out`` are WRITTEN by the reduce launch (no zero-fill launch before it); fresh bag-level products without column sums
+    are always written."""
+    problems = [(_c(p[0]), _c(p[1])) + tuple(p[2:]) + (None,) * (6 - len(p)) for p in problems]
+    _need_cuda(*(t for p in problems for t in p[:2]))
+    if any(p[0].shape[1] % (16 // p[0].element_size()) for p in problems):     # narrow heads (N1 = 2): gemm_tn pads them
+        assert all(p[5] is None for p in problems), "scale / deinterleave / overwrite need the grouped launch"
         return [gemm_tn(A, B, out=out, colsum_into=ci, colsum_parts=cp) for A, B, out, ci, cp, _ in problems]
-    n = len(problems)
-    arr = (_lib.TnProblem * n)()
-    keep, Cs = [], []
-    for g, (A, B, out, ci, cp, opts) in enumerate(problems):
-        _need_cuda(A, B)
-        A, B = _c(A), _c(B)
-        M, N1 = A.shape
-        N2 = B.shape[1]
-        flags, scale = 0, 1.0
-        if out is None and fresh:
-            C = torch.empty((N1, N2), dtype=torch.float32, device=A.device)
-            flags |= _lib.TN_OVERWRITE
-        else:
-            C = out if out is not None else torch.zeros((N1, N2), dtype=torch.float32, device=A.device)
-        assert C.dtype == torch.float32 and C.is_contiguous() and tuple(C.shape) == (N1, N2)
-        if ci is not None:
-            assert ci.dtype == torch.float32 and ci.is_contiguous() and ci.numel() == N1
-        if opts:
-            if opts.get("scale") is not None:
-                flags, scale = flags | _lib.TN_SCALE, float(opts["scale"])
-            if opts.get("deinterleave"):
-                flags |= _lib.TN_DEINTERLEAVE
-            if opts.get("overwrite"):
-                flags |= _lib.TN_OVERWRITE
-        keep.append((A, B, cp))
-        Cs.append(C)
-        arr[g] = _lib.TnProblem(ptr(A), ptr(B), ptr(C), ptr(cp[0]) if cp else None, ptr(ci), M, N1, N2, N1, N2, N2, cp[1] if cp else 0,
-                                flags, scale)
-    wsb = _lib.lib().murcl_gemm_tn_grouped_workspace_bytes(arr, n, BF16)
-    assert wsb, "gemm_tn_grouped_ok and the library disagree"
-    ws = torch.empty((wsb // 4,), dtype=torch.float32, device=Cs[0].device)
-    with _span(lambda: (f"gemm_tn_sq_grouped{n}<bf16>",
-               dict(flops=sum(2.0 * A.shape[0] * A.shape[1] * B.shape[1] for A, B, _ in keep),
-                    bytes=sum(A.shape[0] * (A.shape[1] + B.shape[1]) * 2 + A.shape[1] * B.shape[1] * 4 for A, B, _ in keep)))):
-        check(_lib.lib().murcl_gemm_tn_grouped(arr, n, BF16, ptr(ws), wsb, stream()), "gemm_tn_grouped")
-    return Cs
-
-
-def gemm_tn_small_grouped_ok(problems):
-    """2-4 f32 products of at most 512 rows each (bag-level / rollout-level weight gradients), accumulated into their outputs:
-    ONE launch of the 32 x 32-tile single-writer kernel over all their tiles."""
-    if not (_TN_SMALL_GROUP and 1 < len(problems) <= 4):
-        return False
-    for p in problems:
-        A, B = p[0], p[1]
-        if not (A.dtype == torch.float32 and B.dtype == torch.float32 and A.dim() == 2 and B.dim() == 2 and 0 < A.shape[0] <= 512
-                and A.shape[0] == B.shape[0] and A.shape[1] % 4 == 0 and B.shape[1] % 4 == 0 and p[4] is None and not p[5]):
-            return False
-    return True
+    code = dt(problems[0][0])
+    plan = gemm_tn_plan(problems, code)
+    sq_group = _tn_sq_group(plan[2])
+    return _tn_run(problems, code, plan, lambda k, p: (k == _lib.TN_KIND_SMALL and p[3] is None)
+                   or (k == _lib.TN_KIND_SQUARE and fresh and sq_group))
 
 
 def gemm_tn_grouped_ok(problems):
-    """Does this list run as ONE grouped launch?  (bf16, 2-4 products, N1 and N2 multiples of 256, M >= 16384, at most 32 tiles each,
-    all (product, tile) pairs within one round of workgroups.)"""
-    if not (_TN_SQ and 1 < len(problems) <= 4):
-        return False
-    pairs = 0
-    for p in problems:
-        A, B, ci, cp = p[0], p[1], p[3], p[4]
-        if not (A.dtype == torch.bfloat16 and B.dtype == torch.bfloat16 and A.shape[1] % 256 == 0 and B.shape[1] % 256 == 0
-                and A.shape[0] >= 16384 and A.shape[0] == B.shape[0] and (cp is None or ci is not None)):
-            return False
-        tiles = (A.shape[1] // 256) * (B.shape[1] // 256)
-        if tiles > cu_budget() // 8:
-            return False
-        pairs += tiles
-    return pairs <= cu_budget()
+    """Does this list run as ONE grouped square-tile launch?  (murcl_gemm_tn_plan: every product of the square-tile kind, 2-4 of them.)"""
+    problems = [tuple(p) + (None,) * (6 - len(p)) for p in problems]
+    _, wsb, kinds = gemm_tn_plan(problems, dt(problems[0][0]))
+    return wsb >= 0 and _tn_sq_group(kinds)
 
 
 def cu_budget():
@@ -995,9 +947,6 @@ def gru_gates_bwd_into(dh, gates, gh, hprev, dgi, dgh, dhprev=None, accumulate=F
     assert all(t.is_contiguous() for t in (dh, gates, gh, dgi, dgh)) and (dhprev is None or dhprev.is_contiguous())
     check(_lib.lib().murcl_gru_gates_bwd_into(ptr(dh), ptr(gates), ptr(gh), ptr(hprev), ptr(dgi), ptr(dgh), ptr(dhprev), B, H,
                                               int(gh.shape[0] == 1 and B != 1), int(accumulate), stream()), "gru_gates_bwd_into")
-
-
-_TN_SMALL_GROUP = True    # test hook: bag-level f32 weight gradients through the single-writer 32 x 32 kernel
 
 
 def gru_step_ok(B, H, Kx=0):

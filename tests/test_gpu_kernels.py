@@ -267,16 +267,17 @@ def test_gemm_tn_adds_the_bias_gradient_in_the_same_launch(dtype, M, N1, N2):
 
 
 @pytest.mark.parametrize("dtype,M,N1,N2", [(torch.bfloat16, 262144, 128, 512), (torch.float32, 131072, 128, 1024), (torch.bfloat16, 16384, 128, 512)])
-def test_gemm_tn_split_sums_are_the_same_on_every_call(dtype, M, N1, N2):
+def test_gemm_tn_split_parts_plan_and_sums_are_the_same_on_every_call(dtype, M, N1, N2):
     """More than one M-split on the 128 x 128 kernel over >= 16384 rows (the attention weight gradient of the headline step:
     [262144 x 128]^T [. x 512], 64 splits): the partial tiles meet in a fixed order, so repeated calls give bit-identical weight
     and bias gradients."""
     from murcl_amd import _lib, ops
     dev = _dev()
-    assert _lib.lib().murcl_gemm_tn_parts_bytes(M, N1, N2, _lib.BF16 if dtype == torch.bfloat16 else _lib.F32) > 0
     g = torch.Generator(device=dev).manual_seed(7)
     A = torch.randn((M, N1), generator=g, device=dev).to(dtype)
     B = torch.randn((M, N2), generator=g, device=dev).to(dtype)
+    _, ws, kinds = ops.gemm_tn_plan([(A, B, None, None, None, None)], _lib.dt(A))
+    assert ws > 0 and kinds == [_lib.TN_KIND_PARTS]
     runs = []
     for _ in range(3):
         cs = torch.zeros((N1,), device=dev)
@@ -1017,10 +1018,10 @@ def test_dsmil_argmax_first_index_of_the_maximum(B, N, C, ld):
     assert torch.equal(ops.dsmil_argmax(s.view(B * N, ld).to(dev), B, N, C).cpu(), m.cpu())
 
 
-def test_small_f32_weight_gradients_in_one_launch():
+def test_small_f32_weight_gradients_planned_as_one_launch():
     """ops.gemm_tn_grouped on 2-4 f32 products of a few hundred rows (a PPO epoch's weight gradients): one launch of the 32 x 32
     single-writer kernel; products and column sums are ADDED to what the outputs hold."""
-    from murcl_amd import ops
+    from murcl_amd import _lib, ops
     dev = _dev()
     shapes = [(320, 2048, 512, True), (320, 512, 2048, True), (320, 1536, 512, True), (256, 1536, 512, False)]
     for n in (2, 3, 4):
@@ -1031,7 +1032,8 @@ def test_small_f32_weight_gradients_in_one_launch():
             out, ci = C0.to(dev).clone(), (c0.to(dev).clone() if cs else None)
             probs.append((A.to(dev), B.to(dev), out, ci, None))
             want.append((C0.double() + A.double().t() @ B.double(), c0.double() + A.double().sum(0) if cs else None))
-        assert ops.gemm_tn_small_grouped_ok([tuple(p) + (None,) for p in probs])
+        _, ws, kinds = ops.gemm_tn_plan([tuple(p) + (None,) for p in probs], _lib.F32)
+        assert ws == 0 and kinds == [_lib.TN_KIND_SMALL] * n and n <= _lib.TN_MAXG      # all small tiles: one launch
         Cs = ops.gemm_tn_grouped(probs)
         for (A, B, out, ci, _), C, (wC, wc) in zip(probs, Cs, want):
             assert C.data_ptr() == out.data_ptr()
