@@ -102,8 +102,55 @@ def _final(*params):
 
 
 def _direct(p):
-    # (non-leaf tensors - a row of ``attention.2`` handed to one head of ABMIL(K > 1) - have no pre-seated gradient)
-    return _DIRECT and p is not None and p.is_leaf and p.grad is not None and p.grad.is_contiguous() and p.grad.dtype == torch.float32
+    """Does this backward pass add p's gradient into its pre-seated ``.grad`` itself (and hand autograd None)?  Only in direct mode,
+    for a leaf whose ``.grad`` is a contiguous f32 buffer, and only when the pass accumulates into p at all: ``backward(inputs=[x])``
+    and ``autograd.grad(loss, [x])`` leave p's AccumulateGrad node out, ``autograd.grad(loss, [p])`` hands p's gradient back instead
+    (the engine's query raises for a leaf it captures).  One answer per parameter and backward pass (graph task), not one per call:
+    ``_enter(ctx)`` at the top of a backward answers for the Function's own leaf inputs from its graph edges; a parameter it did not
+    cover is looked up through its gradient edge (a view op to reach the accumulator node)."""
+    if not _DIRECT or p is None:
+        return False
+    if torch._C._current_graph_task_id() != _ACC_TASK:
+        _new_task()
+    hit = _ACC.get(id(p))
+    if hit is None:
+        hit = _ACC[id(p)] = _seated(p) and _will_execute(torch.autograd.graph.get_gradient_edge(p).node)
+    return hit
+
+
+# (non-leaf tensors - a row of ``attention.2`` handed to one head of ABMIL(K > 1) - have no pre-seated gradient)
+def _seated(p):
+    return p.is_leaf and p.requires_grad and p.grad is not None and p.grad.is_contiguous() and p.grad.dtype == torch.float32
+
+
+_ACC_TASK, _ACC = -1, {}
+_ACC_NODE = torch._C._functions.AccumulateGrad
+
+
+def _new_task():
+    global _ACC_TASK
+    _ACC_TASK = torch._C._current_graph_task_id()
+    _ACC.clear()
+
+
+def _will_execute(node):
+    try:
+        return torch._C._will_engine_execute_node(node)
+    except RuntimeError:
+        return False
+
+
+def _enter(ctx):
+    """Called first by a backward that may accumulate directly: the ``_direct`` answers for every leaf input of the Function."""
+    if not _DIRECT:
+        return
+    if torch._C._current_graph_task_id() != _ACC_TASK:
+        _new_task()
+    for fn, _ in ctx.next_functions:
+        if type(fn) is _ACC_NODE:
+            v = fn.variable
+            if id(v) not in _ACC:
+                _ACC[id(v)] = _seated(v) and _will_execute(fn)
 
 
 # Which parameters received a gradient since their optimizer last stepped.  torch.optim.Adam skips parameters whose
@@ -264,6 +311,7 @@ class LinearFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
+        _enter(ctx)
         x2, w, y, b = ctx.saved_tensors
         dy2 = _flat2(dy).contiguous()
         if ctx.relu:
@@ -370,6 +418,9 @@ class ABMILFn(torch.autograd.Function):
                               b1, b2, b3, bb, bd, wat, w3t, w2t)
         ctx.dims = (B, N, d)
         ctx.pool_fast = pool_fast
+        # the layout of the K = 512 weight views (wac, w3t, w2t) travels on ctx: ``ops.is_frag`` reads a Python attribute of the
+        # tensor object, which a saved-tensor hook that copies (save_on_cpu, a clone) does not carry over to what backward unpacks
+        ctx.wfrag = ops.is_frag(wac)
         # the surviving entries of a keep mask all equal 1/keep: the masked dgrads below run unscaled and the (linear) factors
         # are applied to the few gradients behind them
         ctx.drop_scale = None
@@ -384,16 +435,18 @@ class ABMILFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, _datt, _dstats):
+        _enter(ctx)
         if dout is None:
             return (None,) * 15
         if ctx.drop_scale is not None or not ctx.pool_fast:
             return ABMILFn._backward_general(ctx, dout) + (None,)
-        return ABMILFn._backward_default(ctx.saved_tensors, ctx.dims, dout, ctx.needs_input_grad[0]) + (None, None)
+        return ABMILFn._backward_default(ctx.saved_tensors, ctx.dims, dout, ctx.needs_input_grad[0], ctx.wfrag) + (None, None)
 
     @staticmethod
-    def _backward_default(saved, dims, dout, need_dx):
+    def _backward_default(saved, dims, dout, need_dx, wfrag):
         """The backward pass of the default configuration on explicit tensors (``ABMILFn.backward`` hands it one call's saved
-        tensors, ``EncoderSession`` the activations of all patch steps of a training step as one batch)."""
+        tensors, ``EncoderSession`` the activations of all patch steps of a training step as one batch).  ``wfrag``: wac, w3t and
+        w2t are fragment-order views (``ops.is_frag`` of the forward's views)."""
         (x2, h1, h2, h3, scores, A, M, ml, out, w1, w2, w3, wa, ba, wb, wd, wac, m1, m2, m3,
          b1, b2, b3, bb, bd, wat, w3t, w2t) = saved
         B, N, d = dims
@@ -412,9 +465,10 @@ class ABMILFn(torch.autograd.Function):
         # The row scale of the rank-1 term below is A = softmax(s)/sqrt(N), which the forward pass no longer forms: the bf16 panel
         # kernel makes it from the raw scores and (m, l) in its epilogue; the f32 GEMM takes the rows this pass leaves behind
         if m3 is not None:
-            dT, dba, dwb, dbb = ops.abmil_pool_bwd(h3.view(B, N, L), wac, ba, wb, scores, ml, M, dM, into=into_k2)
+            dT, dba, dwb, dbb = ops.abmil_pool_bwd(h3.view(B, N, L), wac, ba, wb, scores, ml, M, dM, into=into_k2, frag=wfrag)
         else:
-            dT, dba, dwb, dbb, A = ops.abmil_pool_bwd(h3.view(B, N, L), wac, ba, wb, scores, ml, M, dM, into=into_k2, want_A=True)
+            dT, dba, dwb, dbb, A = ops.abmil_pool_bwd(h3.view(B, N, L), wac, ba, wb, scores, ml, M, dM, into=into_k2, want_A=True,
+                                                      frag=wfrag)
         dwa = _wgrad(dT, h3, wa)
         if direct_k2:
             _touch(ba, wb, bb)
@@ -434,17 +488,18 @@ class ABMILFn(torch.autograd.Function):
             # workgroups, one reduce launch: ops.gemm_tn_grouped) unless a data-parallel reducer asked for per-layer milestones
             grouped = _GROUP_WGRAD and _MILESTONE is None
             dz3, _, db3 = ops.panel_gemm(dT, wat, ops.PG_RANK1_MASK, bitmask=m3, rowscale=scores.view(-1), bias=ml, rank1=dM,
-                                         rows_per_bag=N, colsum=True, colsum_into=None if f3 else into(b3), colsum_defer=f3)
+                                         rows_per_bag=N, colsum=True, colsum_into=None if f3 else into(b3), colsum_defer=f3,
+                                         frag=False)
             if not grouped:
                 dw3 = _wgrad(dz3, h2, w3, b3, db3 if f3 else None)
                 _final(w3, b3)
             dz2, _, db2 = ops.panel_gemm(dz3, w3t, ops.PG_MASK, bitmask=m2, colsum=True,
-                                         colsum_into=None if f2 else into(b2), colsum_defer=f2)
+                                         colsum_into=None if f2 else into(b2), colsum_defer=f2, frag=wfrag)
             if not grouped:
                 dw2 = _wgrad(dz2, h1, w2, b2, db2 if f2 else None)
                 _final(w2, b2)
             dz1, _, db1 = ops.panel_gemm(dz2, w2t, ops.PG_MASK, bitmask=m1, colsum=True,
-                                         colsum_into=None if f1 else into(b1), colsum_defer=f1)
+                                         colsum_into=None if f1 else into(b1), colsum_defer=f1, frag=wfrag)
             budget_scope.__exit__()                                # the grouped weight gradients run behind the collective: full chip
             if grouped:
                 dw3, dw2, dw1 = _wgrad_group([(dz3, h2, w3, b3, db3 if f3 else None), (dz2, h1, w2, b2, db2 if f2 else None),
@@ -494,11 +549,12 @@ class ABMILFn(torch.autograd.Function):
         dpre = ops.relu_bwd(dout.contiguous(), out)
         dwd, dbd = ops.gemm_tn(dpre, M), ops.colsum(dpre)
         dM = ops.gemm_nt(dpre, ops.transposed(wd))
+        fr = ctx.wfrag
         if ctx.pool_fast and m3 is not None:
-            dT, dba, dwb, dbb = ops.abmil_pool_bwd(h3.view(B, N, L), wac, ba, wb, scores, ml, M, dM)
+            dT, dba, dwb, dbb = ops.abmil_pool_bwd(h3.view(B, N, L), wac, ba, wb, scores, ml, M, dM, frag=fr)
             dwb = dwb.reshape(1, -1)
         elif ctx.pool_fast:
-            dT, dba, dwb, dbb, A = ops.abmil_pool_bwd(h3.view(B, N, L), wac, ba, wb, scores, ml, M, dM, want_A=True)
+            dT, dba, dwb, dbb, A = ops.abmil_pool_bwd(h3.view(B, N, L), wac, ba, wb, scores, ml, M, dM, want_A=True, frag=fr)
             dwb = dwb.reshape(1, -1)
         else:
             U, Asm = scores, ml
@@ -511,11 +567,12 @@ class ABMILFn(torch.autograd.Function):
         if m3 is not None:
             if ctx.pool_fast:
                 dz3, _, db3 = ops.panel_gemm(dT, wat, ops.PG_RANK1_MASK, bitmask=m3, rowscale=scores.view(-1), bias=ml, rank1=dM,
-                                             rows_per_bag=N, colsum=True)
+                                             rows_per_bag=N, colsum=True, frag=False)
             else:
-                dz3, _, db3 = ops.panel_gemm(dT, wat, ops.PG_RANK1_MASK, bitmask=m3, rowscale=A.view(-1), rank1=dM, rows_per_bag=N, colsum=True)
-            dz2, _, db2 = ops.panel_gemm(dz3, w3t, ops.PG_MASK, bitmask=m2, colsum=True)
-            dz1, _, db1 = ops.panel_gemm(dz2, w2t, ops.PG_MASK, bitmask=m1, colsum=True)
+                dz3, _, db3 = ops.panel_gemm(dT, wat, ops.PG_RANK1_MASK, bitmask=m3, rowscale=A.view(-1), rank1=dM, rows_per_bag=N, colsum=True,
+                                             frag=False)
+            dz2, _, db2 = ops.panel_gemm(dz3, w3t, ops.PG_MASK, bitmask=m2, colsum=True, frag=fr)
+            dz1, _, db1 = ops.panel_gemm(dz2, w2t, ops.PG_MASK, bitmask=m1, colsum=True, frag=fr)
         else:
             dz3, ws = ops.gemm_nt(dT, wat, epi=ops.EPI_RANK1_MASK, mask=h3, rowscale=A.view(-1), rank1=dM, rows_per_bag=N, colsum=True)
             db3 = ops.colsum(ws)
@@ -607,6 +664,7 @@ class ABMILStepFn(torch.autograd.Function):
         scores, part = ops.abmil_pool_partials(h3.view(B, N, s.L), wac, ba, wb, bb, scores=blk(s.scores))
         out, _, ml = ops.abmil_pool_decoder(part, B, N, T, wd, bd, out=(blk(s.out), blk(s.M), blk(s.ml)))
         s.weights = (w1, w2, w3, wa, ba, wb, wd, wac, b1, b2, b3, bb, bd, wat, w3t, w2t)
+        s.wfrag = ops.is_frag(wac)
         s.t, s.pending = t + 1, s.pending + 1
         ctx.session, ctx.t = s, t
         ctx.mark_non_differentiable(scores, ml)
@@ -624,6 +682,7 @@ class ABMILStepFn(torch.autograd.Function):
         if all(g is None for g in s.dout[:n]):
             return (None,) * 14
         like = next(g for g in s.dout[:n] if g is not None)
+        _enter(ctx)                                                                  # (every step's node has the same parameter inputs)
         from .utils.views import adjacent as _adjacent, as_one as _as_one       # (module level would be a circular import)
         douts = [g if g is not None else torch.zeros_like(like) for g in s.dout[:n]]
         if all(g is not None for g in s.dout[:n]) and _adjacent(douts):
@@ -634,7 +693,7 @@ class ABMILStepFn(torch.autograd.Function):
         R, Bt = n * s.bags * s.N, n * s.bags
         saved = (s.x.view(-1, s.d)[:R], s.h1[:R], s.h2[:R], s.h3[:R], s.scores[:Bt], None, s.M[:Bt], s.ml[:Bt], s.out[:Bt],
                  w1, w2, w3, wa, ba, wb, wd, wac, s.m1[:R], s.m2[:R], s.m3[:R], b1, b2, b3, bb, bd, wat, w3t, w2t)
-        return ABMILFn._backward_default(saved, (Bt, s.N, s.d), dout_all, False) + (None,)
+        return ABMILFn._backward_default(saved, (Bt, s.N, s.d), dout_all, False, s.wfrag) + (None,)
 
 
 class SessionOutFn(torch.autograd.Function):
@@ -698,14 +757,16 @@ class GRUStepFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dh):
+        _enter(ctx)
         x, h_prev, w_ih, w_hh, gates, gh, b_ih, b_hh = ctx.saved_tensors
         dgi, dgh, dhp = ops.gru_gates_bwd(dh.contiguous(), gates, gh, h_prev)
         dx = ops.gemm_nt(dgi, ops.transposed(w_ih)) if ctx.needs_input_grad[0] else None
         dw_ih, db_ih = _wbgrad(dgi, x, w_ih, b_ih)
         if h_prev is None:
             db_hh = _bgrad(dgh, b_hh)
-            _touch(w_hh)                       # nn.GRU from a zero state: a zero gradient, but a gradient (Adam applies decay)
-            dh_prev, dw_hh = None, (None if _direct(w_hh) else torch.zeros_like(w_hh))
+            # nn.GRU from a zero state: a zero gradient, but a gradient (Adam applies decay) - announced here when direct, by
+            # AccumulateGrad's hook otherwise (and not at all when this backward pass does not accumulate into w_hh)
+            dh_prev, dw_hh = None, (_touch(w_hh) if _direct(w_hh) else torch.zeros_like(w_hh))
         else:
             dw_hh, db_hh = _wbgrad(dgh, h_prev, w_hh, b_hh)
             dh_prev = None
@@ -745,6 +806,7 @@ class GRUSeqFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dhs):
+        _enter(ctx)
         x2, w_ih, w_hh, gates, gh, hs, b_ih, b_hh = ctx.saved_tensors
         T, B, H = hs.shape
         dhs = dhs.contiguous()
@@ -774,8 +836,7 @@ class GRUSeqFn(torch.autograd.Function):
         if T > 1:
             dw_hh = _wgrad(dgh2[B:], hs.view(T * B, H)[:-B], w_hh)
         else:
-            _touch(w_hh)
-            dw_hh = None if _direct(w_hh) else torch.zeros_like(w_hh)
+            dw_hh = _touch(w_hh) if _direct(w_hh) else torch.zeros_like(w_hh)        # (_touch returns None)
         return dx, dw_ih, dw_hh, _bgrad(dgi2, b_ih), _bgrad(dgh2, b_hh)
 
 
@@ -809,6 +870,7 @@ class GRUViewSeqFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dhs):
+        _enter(ctx)
         x2, w_ih, w_hh, gates, gh, hs, b_ih, b_hh = ctx.saved_tensors
         B = ctx.B
         R, H = hs.shape
@@ -959,6 +1021,7 @@ class DSMILFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dclasses, dbag, _dm, dcmax=None):
+        _enter(ctx)
         x, Y, m, qmax, A, Z, wv, wq, xm_saved, xv = ctx.saved_tensors
         B, N, d, C, LD, reassoc, qv, dropped = ctx.meta
         if not dropped:
@@ -1260,6 +1323,7 @@ class CLAMFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dM, _dA, _ds, dinst, _dids, _dpt):
+        _enter(ctx)
         x2, h, U, A, M, w1, wa, wb, wc, inst_w, m1 = ctx.saved_tensors
         b1, ba, bb, bc = ctx.bias_params
         B, N, d, L, D = ctx.dims

@@ -233,7 +233,7 @@ def panel_supported(M, N, K, epi, rows_per_bag=0):
 
 def panel_gemm(A, W, epi, *, bias=None, want_bitmask=False, bitmask=None, rowscale=None, rank1=None, rows_per_bag=0,
                colsum=False, colsum_into=None, colsum_defer=False, reverse=False, stream_a=False, out=None, bitmask_out=None,
-               drop=None):
+               drop=None, frag=None):
     """bf16 weight-stationary C = epi(A @ W^T).  Returns (C, bitmask_out or None, colsum or None).
     ``colsum_into`` ([N] f32): the column sums are ADDED to it (gradient accumulation) and returned as None.
     ``colsum_defer``: no second launch - the third result is (partial rows [R,N] f32, R) for ``gemm_tn(colsum_parts=...)``,
@@ -242,9 +242,11 @@ def panel_gemm(A, W, epi, *, bias=None, want_bitmask=False, bitmask=None, rowsca
     ``stream_a``: load A with the non-temporal policy (K = 512): it is read once and should not displace the output, which
     the next kernel reads, from the Infinity Cache.
     ``drop`` (a DropSeed; PG_BIAS_RELU with ``want_bitmask``, K = 512): Dropout behind the ReLU inside the epilogue, the mask
-    never materialised; the bit mask records what survives (= ``dropout_relu_bitmask`` on the output, without that pass)."""
+    never materialised; the bit mask records what survives (= ``dropout_relu_bitmask`` on the output, without that pass).
+    ``frag``: is W a fragment-order view?  None asks ``is_frag(W)``; a backward pass that received W through autograd's saved
+    tensors says so itself (a saved-tensor hook that copies returns a tensor without the tag)."""
     _need_cuda(A, W)
-    wfrag = 4 if is_frag(W) else 0                          # (W in fragment order: walk_reverse bit 2 of the C-ABI)
+    wfrag = 4 if (is_frag(W) if frag is None else frag) else 0     # (W in fragment order: walk_reverse bit 2 of the C-ABI)
     A, W = _c(A), (W if wfrag else _c(W))
     M, K = A.shape
     N = W.shape[0]
@@ -448,12 +450,13 @@ def _pool_work(B, N, L, D, es):
     return dict(flops=B * (2.0 * N * L * D + 2.0 * N * D + 2.0 * N * L), bytes=B * (N * L * es + N * 4 + L * 4) + L * D * es)
 
 
-def abmil_pool_partials(H, Wa, ba, wb, bb, exact_tanh=None, scores=None):
+def abmil_pool_partials(H, Wa, ba, wb, bb, exact_tanh=None, scores=None, frag=None):
     """The K2 streaming pass on its own - ONE launch: H [B,N,512], Wa [128,512] (same dtype) -> raw scores [B,N] f32 and the chunk
     partials ``part`` [B*S*(L+4)] f32 ((sum p.H, m, l) per (bag, row chunk)).  The per-bag merge belongs to the consumer:
-    ``abmil_pool_decoder`` (the training / inference path), or ``abmil_pool_combine`` for A, M, ml as tensors."""
+    ``abmil_pool_decoder`` (the training / inference path), or ``abmil_pool_combine`` for A, M, ml as tensors.
+    ``frag``: is Wa a fragment-order view (None: ``is_frag(Wa)``; see ``panel_gemm``)."""
     _need_cuda(H, Wa)
-    wfrag = 2 if is_frag(Wa) else 0                         # (Wa in fragment order: bit 1 of the C-ABI's exact_tanh / flags argument)
+    wfrag = 2 if (is_frag(Wa) if frag is None else frag) else 0     # (Wa in fragment order: bit 1 of the C-ABI's exact_tanh / flags argument)
     H, Wa = _c(H), (Wa if wfrag else _c(Wa))
     B, N, L = H.shape
     D = Wa.shape[0]
@@ -498,11 +501,11 @@ def abmil_pool_combine(scores, part, dtype, out=None):
     return A, M, ml
 
 
-def abmil_pool_fwd(H, Wa, ba, wb, bb, exact_tanh=None, out=None):
+def abmil_pool_fwd(H, Wa, ba, wb, bb, exact_tanh=None, out=None, frag=None):
     """H [B,N,512], Wa [128,512] (same dtype) -> scores [B,N], A [B,N], M [B,512], ml [B,2] (all f32): the streaming pass and the
     per-bag merge as two launches (stand-alone use; the modules run ``abmil_pool_partials`` + ``abmil_pool_decoder``).
-    ``out`` = (scores, A, M, ml) caller-owned contiguous buffers of those shapes."""
-    scores, part = abmil_pool_partials(H, Wa, ba, wb, bb, exact_tanh, scores=None if out is None else out[0])
+    ``out`` = (scores, A, M, ml) caller-owned contiguous buffers of those shapes.  ``frag``: as ``abmil_pool_partials``."""
+    scores, part = abmil_pool_partials(H, Wa, ba, wb, bb, exact_tanh, scores=None if out is None else out[0], frag=frag)
     A, M, ml = abmil_pool_combine(scores, part, H.dtype, out=None if out is None else out[1:])
     return scores, A, M, ml
 
@@ -549,12 +552,13 @@ def abmil_attention(scores, ml):
     return A
 
 
-def abmil_pool_bwd(H, Wa, ba, wb, scores, ml, M, dM, exact_tanh=None, into=None, want_A=False):
+def abmil_pool_bwd(H, Wa, ba, wb, scores, ml, M, dM, exact_tanh=None, into=None, want_A=False, frag=None):
     """-> dT [B*N,128] (dtype of H; 32 spare rows allocated behind it), dba[128], dwb[128], dbb[1] (, A [B,N] with ``want_A``: the
     normalised attention row softmax(s)/sqrt(N), which the pass has in registers - the rank-1 input gradient's row scale).
-    ``into`` = (dba, dwb, dbb) f32 buffers: the kernel ADDS to them (gradient accumulation) instead of fresh zeros."""
+    ``into`` = (dba, dwb, dbb) f32 buffers: the kernel ADDS to them (gradient accumulation) instead of fresh zeros.
+    ``frag``: is Wa a fragment-order view (None: ``is_frag(Wa)``; see ``panel_gemm``)."""
     _need_cuda(H, Wa, dM)
-    wfrag = 2 if is_frag(Wa) else 0
+    wfrag = 2 if (is_frag(Wa) if frag is None else frag) else 0
     H, Wa, dM = _c(H), (Wa if wfrag else _c(Wa)), _c(dM)
     B, N, L = H.shape
     D = Wa.shape[0]
@@ -1348,9 +1352,6 @@ def cross_entropy(logits, targets, group, want_conf=False):
     return (loss, dl, preds, conf) if want_conf else (loss, dl, preds)
 
 
-_DROP_COUNTER = 0
-
-
 class DropSeed:
     """A dropout keep mask that is never materialised: the (seed, keep probability) its elements are a pure function of."""
     __slots__ = ("seed", "keep_p")
@@ -1366,11 +1367,10 @@ class DropSeed:
 
 
 def dropout_seed():
-    """Seed of the next counter-based dropout mask: torch's global seed and a call counter (no device synchronisation;
-    ``torch.manual_seed`` makes a run reproducible)."""
-    global _DROP_COUNTER
-    _DROP_COUNTER += 1
-    return (torch.initial_seed() * 0x9E3779B97F4A7C15 + _DROP_COUNTER * 0xBF58476D1CE4E5B9) & 0xFFFFFFFFFFFFFFFF
+    """Seed of the next counter-based dropout mask: 63 bits off torch's CPU generator, as ``step_draws`` (no device work;
+    ``torch.manual_seed`` makes a run reproducible).  Being torch's RNG state, it is what ``torch.utils.checkpoint`` saves and
+    restores around its recomputation, so the recomputed forward applies the masks the original forward drew."""
+    return int(torch.empty((), dtype=torch.int64).random_())
 
 
 DRAWS_MAX_B = 2048
@@ -1405,8 +1405,8 @@ def dropout_relu_bitmask(x, drop, want_bits=True):
 
 
 def dropout_mask(shape, dtype, keep_p, device, seed=None):
-    """Keep mask of ``nn.Dropout(1 - keep_p)``: ``1/keep_p`` where kept, 0 where dropped.  Seeded from torch's global
-    seed and a call counter (no device synchronisation; ``torch.manual_seed`` makes a run reproducible)."""
+    """Keep mask of ``nn.Dropout(1 - keep_p)``: ``1/keep_p`` where kept, 0 where dropped.  Seeded from torch's CPU
+    generator (``dropout_seed``: no device synchronisation; ``torch.manual_seed`` makes a run reproducible)."""
     seed = dropout_seed() if seed is None else int(seed)
     out = torch.empty(shape, dtype=dtype, device=device)
     check(_lib.lib().murcl_dropout_mask(ptr(out), out.numel(), float(keep_p), 1.0 / DropSeed(keep_p, seed).keep_q, seed, dt(out), stream()),

@@ -588,7 +588,7 @@ def test_dsmil_dropout_v_training_mode_vs_reference_golden(golden):
     m.keep_mask_v = None
     b1 = m(x)[1].detach().clone()
     b2 = m(x)[1].detach().clone()
-    # its own draws (seed = torch's global seed + a call counter: every call a new mask), around the un-dropped value in the mean
+    # its own draws (seed = the next draw of torch's CPU generator: every call a new mask), around the un-dropped value in the mean
     assert (b1 - b2).abs().max().item() > 1e-3 and (b1 - bag.detach()).abs().max().item() > 1e-3
     m.eval()
     m0 = _dsmil(23, 512, 2)
