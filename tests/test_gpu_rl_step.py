@@ -301,7 +301,8 @@ def test_ppo_returns_sharded_statistics_equal_the_single_kernel():
 def test_native_ppo_sequences_equal_the_per_launch_autograd_path():
     """csrc/ppo_seq.hip (one C call per sampling step / per K_epoch) against the same math driven launch by launch through
     autograd (ActorCritic.evaluate + PPOLossFn, the round-1 path, still used for shapes the sequences do not cover):
-    actions, log-probs, hidden states, and every parameter gradient of one epoch."""
+    actions, log-probs, hidden states, and every parameter gradient of one epoch.
+    (Both paths against float64, on clipped rows and at other shapes: tests/test_gpu_ppo_kernels.py.)"""
     from murcl_amd.models.rlmil import PPO, ActorCritic, Memory, _HipPolicyKernels
     dev = torch.device("cuda:0")
     seed, B, S_, H, K, Tm = 57, 12, 512, 512, 10, 4
