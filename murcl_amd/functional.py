@@ -4,6 +4,7 @@ Forward and backward are sequences of C-ABI launches (murcl_amd.ops); torch supp
 only tensor storage and the autograd graph.  No CPU / eager-PyTorch fallback exists:
 CPU tensors raise.
 """
+import contextlib
 import math
 
 import torch
@@ -329,6 +330,145 @@ class LinearFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
+def _dropout(h, k, bits):
+    """Dropout after a ReLU, in place: h *= keep for ``k`` = a DropSeed or a materialised keep-multiplier tensor.  -> the 1-bit mask
+    of the surviving positive entries when ``bits`` (bf16 fast path), else None."""
+    seeded = isinstance(k, ops.DropSeed)
+    if seeded and h.shape[0] % 32 == 0 and h.shape[1] % 128 == 0:
+        return ops.dropout_relu_bitmask(h, k, want_bits=bits)
+    ops.mul(h, ops.dropout_mask(h.shape, h.dtype, k.keep_p, h.device, seed=k.seed) if seeded else k.to(h.dtype).reshape(h.shape))
+    return ops.relu_bitmask(h) if bits else None
+
+
+def _abmil_fast_forward(x2, B, N, params, *, views=None, bits=True, drops=None, blocks=None):
+    """The bf16 fast chain of ``ABMILFn`` and ``ABMILStepFn`` (shapes ``abmil_fast_path`` accepts): three weight-stationary encoder
+    GEMMs that also emit 1-bit ReLU masks, the one-pass pooling kernel, the decoder.  ``views``: the seven weight views when the
+    caller had to make them itself; ``bits``: write the masks (a backward pass can follow); ``drops``: as ``ABMILFn.forward``;
+    ``blocks`` = (h1, h2, h3, m1, m2, m3, scores, (out, M, ml)): caller-owned result buffers (``EncoderSession``).
+    -> (h1, h2, h3, m1, m2, m3, scores, M, ml, out, views)"""
+    w1, b1, w2, b2, w3, b3, wa, ba, wb, bb, wd, bd = params
+    T = x2.dtype
+    if views is None:
+        # compute-dtype copies of W1..W3, Wa for this pass and W2^T, W3^T, Wa^T for the dgrads of the backward pass: one
+        # launch, and only when a parameter changed since they were last built (ops.weight_views)
+        views = ops.weight_views(_frag_specs(w1, w2, w3, wa, T) if _FRAG_WEIGHTS else
+                                 [(w, False, T) for w in (w1, w2, w3, wa)] + [(wa, True, T), (w3, True, T), (w2, True, T)])
+    w1c, w2c, w3c, wac = views[:4]
+    o1, o2, o3, bm1, bm2, bm3, sc, triple = blocks or (None,) * 8
+    nt = _STREAM_A
+    own = bits and drops is None                 # with Dropout the pass that applies it writes the mask of what survives
+    h1, m1, _ = ops.panel_gemm(x2, w1c, ops.PG_BIAS_RELU, bias=b1, want_bitmask=own, stream_a=bool(nt & 1), out=o1, bitmask_out=bm1)
+    if drops is not None:
+        m1 = _dropout(h1, drops[0], bits)
+    # layer 2 walks the rows backwards (layer 1 has just written the high rows of h1), layer 3 forwards again,
+    # and the pooling kernel backwards: every pass starts on what its producer left in the Infinity Cache
+    h2, m2, _ = ops.panel_gemm(h1, w2c, ops.PG_BIAS_RELU, bias=b2, want_bitmask=own, reverse=True, stream_a=bool(nt & 2),
+                               out=o2, bitmask_out=bm2)
+    if drops is not None:
+        m2 = _dropout(h2, drops[1], bits)
+    h3, m3, _ = ops.panel_gemm(h2, w3c, ops.PG_BIAS_RELU, bias=b3, want_bitmask=bits, stream_a=bool(nt & 4), out=o3, bitmask_out=bm3)
+    # ONE launch for the K2 row (scores + chunk partials); the per-bag merge is part of the decoder launch below and the
+    # normalised attention row is formed by the backward pass (or on demand: ``attention_rows``)
+    scores, part = ops.abmil_pool_partials(h3.view(B, N, h3.shape[1]), wac, ba, wb, bb, scores=sc)
+    out, M, ml = ops.abmil_pool_decoder(part, B, N, T, wd, bd, out=triple)
+    return h1, h2, h3, m1, m2, m3, scores, M, ml, out, views
+
+
+def _abmil_backward(saved, dims, dout, need_dx, wfrag, *, pool_fast, drop_scale):
+    """The aggregator's backward pass on explicit tensors: ``ABMILFn.backward`` hands it one call's saved tensors, ``EncoderSession``
+    the activations of all patch steps of a training step as one batch.  ``wfrag``: wac, w3t and w2t are fragment-order views
+    (``ops.is_frag`` of the forward's views).  ``pool_fast`` / ``drop_scale``: as ``ABMILFn.forward`` left them on ctx.
+    -> (dx, dw1, db1, dw2, db2, dw3, db3, dwa, dba, dwb, dbb, dwd, dbd)"""
+    (x2, h1, h2, h3, scores, A, M, ml, out, w1, w2, w3, wa, ba, wb, wd, wac, m1, m2, m3,
+     b1, b2, b3, bb, bd, wat, w3t, w2t) = saved
+    B, N, d = dims
+    T = x2.dtype
+    L = h3.shape[1]
+    panel = m3 is not None           # the bf16 fast chain (so ``pool_fast``: abmil_fast_path): bit-mask panel dgrads; else row-major GEMMs
+    # Where each gradient goes.  The tuned default (no dropout, L = 512, D = 128) lets the routing helpers add into pre-seated
+    # ``.grad`` buffers, defer and fire milestones.  The other configurations (``--dropout`` > 0 while training, other ``--L`` /
+    # ``--D``) get every gradient back as its own tensor - the dropout factors are applied to them at the end: with None in the
+    # parameter's place the same helpers neither accumulate (``_direct(None)`` is False), defer, nor fire.
+    default = pool_fast and drop_scale is None
+    pw1, pb1, pw2, pb2, pw3, pb3, pwa, pba, pwb, pbb, pwd, pbd = \
+        (w1, b1, w2, b2, w3, b3, wa, ba, wb, bb, wd, bd) if default else (None,) * 12
+    # the three encoder weight gradients wait until the last input gradient exists and run as ONE grouped launch (one round of
+    # workgroups, one reduce launch: ops.gemm_tn_grouped) unless a data-parallel reducer asked for per-layer milestones; the general
+    # configurations keep one launch per layer (a grouped launch is another kernel: other numerics)
+    grouped = _GROUP_WGRAD and _MILESTONE is None and default and panel
+
+    def dgrad(dy, wt, bits, h, w, b, frag, **rank1):
+        """dZ = (dy Wt^T [+ the rank-1 term]) * relu'(H) and the bias gradient of H's layer -> (dZ, db, rows): db is None when it went
+        into b.grad or waits in ``rows``, the per-workgroup partial column sums that the layer's weight gradient adds up in its
+        reduce launch (weight AND bias accumulate directly: ``_FOLD_BIAS``)."""
+        if bits is None:
+            dz, ws = ops.gemm_nt(dy, wt, epi=ops.EPI_RANK1_MASK if rank1 else ops.EPI_MASK, mask=h, colsum=True, **rank1)
+            return dz, _bgrad(ws, b), None
+        fold = _FOLD_BIAS and _direct(w) and _direct(b)
+        into = None
+        if not fold and _direct(b):                                   # the bias gradient straight from the epilogue
+            _touch(b)
+            into = b.grad.view(-1)
+        dz, _, cs = ops.panel_gemm(dy, wt, ops.PG_RANK1_MASK if rank1 else ops.PG_MASK, bitmask=bits, colsum=True, colsum_into=into,
+                                   colsum_defer=fold, frag=frag, **rank1)
+        return (dz, None, cs) if fold else (dz, cs, None)
+
+    # decoder (bag level, f32)
+    dpre = ops.relu_bwd(dout.contiguous(), out)
+    dwd, dbd = _wbgrad(dpre, M, pwd, pbd)
+    dM = ops.gemm_nt(dpre, ops.transposed(wd))
+    # attention pooling.  From here to the last input gradient a data-parallel step has the head group's all-reduce in flight:
+    # these launches leave its channel workgroups their CUs (_overlap_budget: a no-op on one GPU; the default configuration only)
+    with _overlap_budget() if default else contextlib.nullcontext():
+        direct_k2 = _direct(pba) and _direct(pwb) and _direct(pbb)      # the kernel's atomics add straight into the grads
+        if pool_fast:
+            # The row scale of the rank-1 term below is A = softmax(s)/sqrt(N), which the forward pass did not form: the bf16 panel
+            # kernel makes it from the raw scores and (m, l) in its epilogue; the f32 GEMM takes the rows this pass leaves behind
+            dT, dba, dwb, dbb, *att = ops.abmil_pool_bwd(h3.view(B, N, L), wac, ba, wb, scores, ml, M, dM, want_A=not panel, frag=wfrag,
+                                                          into=(ba.grad, wb.grad.view(-1), bb.grad) if direct_k2 else None)
+            A = att[0] if att else None
+        else:
+            # any L / D: the generic pooling chain backwards (the forward pass saved U and the soft-max rows as scores, ml; and A)
+            dA = ops.rows_dot(h3.view(B, N, L), dM.view(B, 1, L)).view(B, N)
+            dAs = ops.mul(dA, torch.full_like(dA, 1.0 / (N ** 0.5)))                               # A = softmax / sqrt(N)
+            ds = ops.softmax_rows_bwd(ml, dAs).view(-1)
+            dT, dwb, dbb, dba = ops.gated_score_bwd(scores, wb.reshape(-1).contiguous(), ds, gated=False)
+            dba = dba.contiguous()
+        dwa = _wgrad(dT, h3, pwa)
+        if direct_k2:
+            _touch(ba, wb, bb)
+            _final(wa, ba, wb, bb, wd, bd)
+        # encoder layer 3: dZ3 = (dT Wa + A (x) dM) * relu'(H3)
+        row_scale = dict(rowscale=scores.view(-1), bias=ml) if panel else dict(rowscale=A.view(-1))
+        dz3, db3, rows3 = dgrad(dT, wat, m3, h3, pw3, pb3, False, rank1=dM, rows_per_bag=N, **row_scale)
+        if not grouped:
+            dw3 = _wgrad(dz3, h2, pw3, pb3, rows3)
+            _final(pw3, pb3)
+        dz2, db2, rows2 = dgrad(dz3, w3t, m2, h2, pw2, pb2, wfrag)
+        if not grouped:
+            dw2 = _wgrad(dz2, h1, pw2, pb2, rows2)
+            _final(pw2, pb2)
+        dz1, db1, rows1 = dgrad(dz2, w2t, m1, h1, pw1, pb1, wfrag)
+    # behind the collective: full chip
+    if grouped:
+        dw3, dw2, dw1 = _wgrad_group([(dz3, h2, w3, b3, rows3), (dz2, h1, w2, b2, rows2), (dz1, x2, w1, b1, rows1)])
+        _final(w3, b3, w2, b2, w1, b1)
+    else:
+        dw1 = _wgrad(dz1, x2, pw1, pb1, rows1)
+    dx = ops.gemm_nt(dz1, ops.transpose_cast(w1, T)).view(B, N, d) if need_dx else None
+    if direct_k2:
+        dba = dwb = dbb = None
+    else:
+        dba, dwb, dbb = _pgrad(dba, pba), _pgrad(dwb.reshape(1, -1), pwb), _pgrad(dbb, pbb)
+    if drop_scale is not None:
+        # dZ2 = (dZ3 W3) * relu'(H2) * keep2 and dZ1 = (dZ2 W2) * relu'(H1) * keep1, the masks above hold relu' AND kept
+        s2 = drop_scale[1]
+        s1 = drop_scale[0] * s2
+        dw2, db2, dw1, db1 = dw2 * s2, db2 * s2, dw1 * s1, db1 * s1
+        dx = dx * s1 if dx is not None else None
+    return dx, dw1, db1, dw2, db2, dw3, db3, dwa, dba, dwb, dbb, dwd, dbd
+
+
 class ABMILFn(torch.autograd.Function):
     """Whole ABMIL.bag_forward for a batch of equal-length bags (models/abmil.py:35-45).
 
@@ -349,71 +489,48 @@ class ABMILFn(torch.autograd.Function):
         x2 = x.reshape(B * N, d)
         L = w3.shape[0]
         pool_fast = (L == 512 and wa.shape[0] == 128)       # the one-pass K2 kernel is built for L = 512, D = 128
-        # compute-dtype copies of W1..W3, Wa for this pass and W2^T, W3^T, Wa^T for the dgrads of the backward pass: one
-        # launch, and only when a parameter changed since they were last built (ops.weight_views)
         wmats = (w1, w2, w3, wa)
         # bf16 + panel-friendly shapes: weight-stationary GEMMs that also emit 1-bit ReLU masks
-        fast = (T == torch.bfloat16 and d == 512 and pool_fast and ops.panel_supported(B * N, L, 512, ops.PG_BIAS_RELU)
-                and ops.panel_supported(B * N, L, 128, ops.PG_RANK1_MASK, N))
-        if all(w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() for w in wmats):
-            tr = [(wa, True, T), (w3, True, T), (w2, True, T)]
-            if T == torch.float32:
-                w1c, w2c, w3c, wac = wmats
-                wat, w3t, w2t = ops.weight_views(tr)
-            elif fast and _FRAG_WEIGHTS:
-                w1c, w2c, w3c, wac, wat, w3t, w2t = ops.weight_views(_frag_specs(w1, w2, w3, wa, T))
-            else:
-                w1c, w2c, w3c, wac, wat, w3t, w2t = ops.weight_views([(w, False, T) for w in wmats] + tr)
-        else:
-            w1c, w2c, w3c, wac = (ops.cast(w.contiguous(), T) for w in wmats)
-            wat, w3t, w2t = (ops.transpose_cast(w, T) for w in (wa, w3, w2))
-        seeded = drops is not None and isinstance(drops[0], ops.DropSeed)
-
-        def drop(h, k, bits):
-            """Dropout after a ReLU, in place: h *= keep.  -> the 1-bit mask of the surviving positive entries (fast path)."""
-            if seeded and h.shape[0] % 32 == 0 and h.shape[1] % 128 == 0:
-                return ops.dropout_relu_bitmask(h, k, want_bits=bits)
-            ops.mul(h, ops.dropout_mask(h.shape, T, k.keep_p, h.device, seed=k.seed) if seeded else k.to(T).reshape(h.shape))
-            return ops.relu_bitmask(h) if bits else None
-
+        fast = abmil_fast_path(B * N, N, d, L, wa.shape[0], T)
+        # compute-dtype copies of W1..W3, Wa for this pass and W2^T, W3^T, Wa^T for the dgrads of the backward pass: one launch,
+        # and only when a parameter changed since they were last built (ops.weight_views; the fast chain asks for its own)
+        tr = [(wa, True, T), (w3, True, T), (w2, True, T)]
+        views = None
+        if not all(w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous() for w in wmats):
+            views = [ops.cast(w.contiguous(), T) for w in wmats] + [ops.transpose_cast(w, T) for w in (wa, w3, w2)]
+        elif T == torch.float32:
+            views = list(wmats) + list(ops.weight_views(tr))
+        elif not fast:
+            views = ops.weight_views([(w, False, T) for w in wmats] + tr)
+        A = None
         if fast:
-            nt = _STREAM_A
             keep = bool(grad_on) and any(ctx.needs_input_grad)     # forward-only passes: no ReLU masks to write
-            h1, m1, _ = ops.panel_gemm(x2, w1c, ops.PG_BIAS_RELU, bias=b1, want_bitmask=keep and drops is None, stream_a=bool(nt & 1))
-            if drops is not None:
-                m1 = drop(h1, drops[0], keep)
-            # layer 2 walks the rows backwards (layer 1 has just written the high rows of h1), layer 3 forwards again,
-            # and the pooling kernel backwards: every pass starts on what its producer left in the Infinity Cache
-            h2, m2, _ = ops.panel_gemm(h1, w2c, ops.PG_BIAS_RELU, bias=b2, want_bitmask=keep and drops is None, reverse=True,
-                                       stream_a=bool(nt & 2))
-            if drops is not None:
-                m2 = drop(h2, drops[1], keep)
-            h3, m3, _ = ops.panel_gemm(h2, w3c, ops.PG_BIAS_RELU, bias=b3, want_bitmask=keep, stream_a=bool(nt & 4))
+            h1, h2, h3, m1, m2, m3, scores, M, ml, out, views = _abmil_fast_forward(
+                x2, B, N, (w1, b1, w2, b2, w3, b3, wa, ba, wb, bb, wd, bd), views=views, bits=keep, drops=drops)
         else:
+            w1c, w2c, w3c, wac = views[:4]
             m1 = m2 = m3 = None
             h1 = ops.gemm_nt(x2, w1c, epi=ops.EPI_BIAS_RELU, bias=b1)
             if drops is not None:
-                drop(h1, drops[0], False)
+                _dropout(h1, drops[0], False)
             h2 = ops.gemm_nt(h1, w2c, epi=ops.EPI_BIAS_RELU, bias=b2)
             if drops is not None:
-                drop(h2, drops[1], False)
+                _dropout(h2, drops[1], False)
             h3 = ops.gemm_nt(h2, w3c, epi=ops.EPI_BIAS_RELU, bias=b3)
-        if pool_fast:
-            # ONE launch for the K2 row (scores + chunk partials); the per-bag merge is part of the decoder launch below and the
-            # normalised attention row is formed by the backward pass (or on demand: ``attention_rows``)
-            scores, part = ops.abmil_pool_partials(h3.view(B, N, L), wac, ba, wb, bb)
-            out, M, ml = ops.abmil_pool_decoder(part, B, N, T, wd, bd)
-            A = None
-        else:
-            # any L / D (abmil.py:8-30 takes them as arguments): the same attention pooling as a chain of the generic kernels -
-            # projection GEMM, tanh score, row soft-max, /sqrt(N) (abmil.py:40-41), weighted row sum
-            U = ops.gemm_nt(h3, wac, epi=ops.EPI_BIAS, bias=ba)                                     # [B*N, D]
-            s = ops.gated_score_fwd(U, wb.reshape(-1).contiguous(), bb, gated=False).view(B, N)
-            Asm = ops.softmax_rows(s)
-            A = ops.mul(Asm, torch.full_like(Asm, 1.0 / (N ** 0.5)), out=torch.empty_like(Asm))
-            M = ops.weighted_rowsum(h3.view(B, N, L), A.view(B, N, 1)).view(B, L)
-            scores, ml = U, Asm                                                                    # what the generic backward needs
-            out = ops.gemm_nt(M, wd, epi=ops.EPI_BIAS_RELU, bias=bd)
+            if pool_fast:
+                scores, part = ops.abmil_pool_partials(h3.view(B, N, L), wac, ba, wb, bb)
+                out, M, ml = ops.abmil_pool_decoder(part, B, N, T, wd, bd)
+            else:
+                # any L / D (abmil.py:8-30 takes them as arguments): the same attention pooling as a chain of the generic kernels -
+                # projection GEMM, tanh score, row soft-max, /sqrt(N) (abmil.py:40-41), weighted row sum
+                U = ops.gemm_nt(h3, wac, epi=ops.EPI_BIAS, bias=ba)                                     # [B*N, D]
+                s = ops.gated_score_fwd(U, wb.reshape(-1).contiguous(), bb, gated=False).view(B, N)
+                Asm = ops.softmax_rows(s)
+                A = ops.mul(Asm, torch.full_like(Asm, 1.0 / (N ** 0.5)), out=torch.empty_like(Asm))
+                M = ops.weighted_rowsum(h3.view(B, N, L), A.view(B, N, 1)).view(B, L)
+                scores, ml = U, Asm                                                                    # what the generic backward needs
+                out = ops.gemm_nt(M, wd, epi=ops.EPI_BIAS_RELU, bias=bd)
+        wac, wat, w3t, w2t = views[3:]
         ctx.save_for_backward(x2, h1, h2, h3, scores, A, M, ml, out, w1, w2, w3, wa, ba, wb, wd, wac, m1, m2, m3,
                               b1, b2, b3, bb, bd, wat, w3t, w2t)
         ctx.dims = (B, N, d)
@@ -438,157 +555,8 @@ class ABMILFn(torch.autograd.Function):
         _enter(ctx)
         if dout is None:
             return (None,) * 15
-        if ctx.drop_scale is not None or not ctx.pool_fast:
-            return ABMILFn._backward_general(ctx, dout) + (None,)
-        return ABMILFn._backward_default(ctx.saved_tensors, ctx.dims, dout, ctx.needs_input_grad[0], ctx.wfrag) + (None, None)
-
-    @staticmethod
-    def _backward_default(saved, dims, dout, need_dx, wfrag):
-        """The backward pass of the default configuration on explicit tensors (``ABMILFn.backward`` hands it one call's saved
-        tensors, ``EncoderSession`` the activations of all patch steps of a training step as one batch).  ``wfrag``: wac, w3t and
-        w2t are fragment-order views (``ops.is_frag`` of the forward's views)."""
-        (x2, h1, h2, h3, scores, A, M, ml, out, w1, w2, w3, wa, ba, wb, wd, wac, m1, m2, m3,
-         b1, b2, b3, bb, bd, wat, w3t, w2t) = saved
-        B, N, d = dims
-        T = x2.dtype
-        L = h3.shape[1]
-        # decoder (bag level, f32)
-        dpre = ops.relu_bwd(dout.contiguous(), out)
-        dwd, dbd = _wbgrad(dpre, M, wd, bd)
-        dM = ops.gemm_nt(dpre, ops.transposed(wd))
-        # attention pooling.  From here to the last input gradient a data-parallel step has the head group's all-reduce in flight:
-        # these launches leave its channel workgroups their CUs (_overlap_budget: a no-op on one GPU)
-        budget_scope = _overlap_budget()
-        budget_scope.__enter__()
-        direct_k2 = _direct(ba) and _direct(wb) and _direct(bb)      # the kernel's atomics add straight into the grads
-        into_k2 = (ba.grad, wb.grad.view(-1), bb.grad) if direct_k2 else None
-        # The row scale of the rank-1 term below is A = softmax(s)/sqrt(N), which the forward pass no longer forms: the bf16 panel
-        # kernel makes it from the raw scores and (m, l) in its epilogue; the f32 GEMM takes the rows this pass leaves behind
-        if m3 is not None:
-            dT, dba, dwb, dbb = ops.abmil_pool_bwd(h3.view(B, N, L), wac, ba, wb, scores, ml, M, dM, into=into_k2, frag=wfrag)
-        else:
-            dT, dba, dwb, dbb, A = ops.abmil_pool_bwd(h3.view(B, N, L), wac, ba, wb, scores, ml, M, dM, into=into_k2, want_A=True,
-                                                      frag=wfrag)
-        dwa = _wgrad(dT, h3, wa)
-        if direct_k2:
-            _touch(ba, wb, bb)
-            _final(wa, ba, wb, bb, wd, bd)
-        # encoder layer 3: dZ3 = (dT Wa + A (x) dM) * relu'(H3)
-        if m3 is not None:
-            def into(b):                                                  # bias gradients straight from the epilogue
-                if _direct(b):
-                    _touch(b)
-                    return b.grad.view(-1)
-                return None
-            # bias gradients: the dgrad kernels leave per-workgroup partial column sums; when weight AND bias accumulate
-            # directly into the flat gradient buffer the rows are added up inside the weight gradient's reduce launch
-            fold = lambda w, b: _FOLD_BIAS and _direct(w) and _direct(b)      # noqa: E731
-            f3, f2, f1 = fold(w3, b3), fold(w2, b2), fold(w1, b1)
-            # the three weight gradients wait until the last input gradient exists and run as ONE grouped launch (one round of
-            # workgroups, one reduce launch: ops.gemm_tn_grouped) unless a data-parallel reducer asked for per-layer milestones
-            grouped = _GROUP_WGRAD and _MILESTONE is None
-            dz3, _, db3 = ops.panel_gemm(dT, wat, ops.PG_RANK1_MASK, bitmask=m3, rowscale=scores.view(-1), bias=ml, rank1=dM,
-                                         rows_per_bag=N, colsum=True, colsum_into=None if f3 else into(b3), colsum_defer=f3,
-                                         frag=False)
-            if not grouped:
-                dw3 = _wgrad(dz3, h2, w3, b3, db3 if f3 else None)
-                _final(w3, b3)
-            dz2, _, db2 = ops.panel_gemm(dz3, w3t, ops.PG_MASK, bitmask=m2, colsum=True,
-                                         colsum_into=None if f2 else into(b2), colsum_defer=f2, frag=wfrag)
-            if not grouped:
-                dw2 = _wgrad(dz2, h1, w2, b2, db2 if f2 else None)
-                _final(w2, b2)
-            dz1, _, db1 = ops.panel_gemm(dz2, w2t, ops.PG_MASK, bitmask=m1, colsum=True,
-                                         colsum_into=None if f1 else into(b1), colsum_defer=f1, frag=wfrag)
-            budget_scope.__exit__()                                # the grouped weight gradients run behind the collective: full chip
-            if grouped:
-                dw3, dw2, dw1 = _wgrad_group([(dz3, h2, w3, b3, db3 if f3 else None), (dz2, h1, w2, b2, db2 if f2 else None),
-                                              (dz1, x2, w1, b1, db1 if f1 else None)])
-                _final(w3, b3, w2, b2, w1, b1)
-            db3, db2 = None if f3 else db3, None if f2 else db2
-            if grouped:
-                db1 = None if f1 else db1
-        else:
-            dz3, ws = ops.gemm_nt(dT, wat, epi=ops.EPI_RANK1_MASK, mask=h3, rowscale=A.view(-1),
-                                  rank1=dM, rows_per_bag=N, colsum=True)
-            db3 = _bgrad(ws, b3)
-            dw3 = _wgrad(dz3, h2, w3)
-            _final(w3, b3)
-            dz2, ws = ops.gemm_nt(dz3, w3t, epi=ops.EPI_MASK, mask=h2, colsum=True)
-            db2 = _bgrad(ws, b2)
-            dw2 = _wgrad(dz2, h1, w2)
-            _final(w2, b2)
-            dz1, ws = ops.gemm_nt(dz2, w2t, epi=ops.EPI_MASK, mask=h1, colsum=True)
-            db1 = _bgrad(ws, b1)
-            budget_scope.__exit__()
-        if m3 is not None and grouped:
-            pass
-        elif m3 is not None and f1:
-            dw1, db1 = _wgrad(dz1, x2, w1, b1, db1), None
-        else:
-            dw1 = _wgrad(dz1, x2, w1)
-        dx = None
-        if need_dx:
-            dx = ops.gemm_nt(dz1, ops.transpose_cast(w1, T)).view(B, N, d)
-        if direct_k2:
-            dba = dwb = dbb = None
-        else:
-            dba, dwb, dbb = _pgrad(dba, ba), _pgrad(dwb.reshape(1, -1), wb), _pgrad(dbb, bb)
-        return dx, dw1, db1, dw2, db2, dw3, db3, dwa, dba, dwb, dbb, dwd, dbd
-
-    @staticmethod
-    def _backward_general(ctx, dout):
-        """The configurations outside the tuned default (``--dropout`` > 0 while training, ``--L`` / ``--D`` other than 512 /
-        128): the same backward pass with every gradient returned to autograd as its own tensor, so that the dropout
-        factors can be applied to them (no direct accumulation into the flat gradient buffer on this path)."""
-        (x2, h1, h2, h3, scores, A, M, ml, out, w1, w2, w3, wa, ba, wb, wd, wac, m1, m2, m3,
-         b1, b2, b3, bb, bd, wat, w3t, w2t) = ctx.saved_tensors
-        B, N, d = ctx.dims
-        T = x2.dtype
-        L = h3.shape[1]
-        dpre = ops.relu_bwd(dout.contiguous(), out)
-        dwd, dbd = ops.gemm_tn(dpre, M), ops.colsum(dpre)
-        dM = ops.gemm_nt(dpre, ops.transposed(wd))
-        fr = ctx.wfrag
-        if ctx.pool_fast and m3 is not None:
-            dT, dba, dwb, dbb = ops.abmil_pool_bwd(h3.view(B, N, L), wac, ba, wb, scores, ml, M, dM, frag=fr)
-            dwb = dwb.reshape(1, -1)
-        elif ctx.pool_fast:
-            dT, dba, dwb, dbb, A = ops.abmil_pool_bwd(h3.view(B, N, L), wac, ba, wb, scores, ml, M, dM, want_A=True, frag=fr)
-            dwb = dwb.reshape(1, -1)
-        else:
-            U, Asm = scores, ml
-            dA = ops.rows_dot(h3.view(B, N, L), dM.view(B, 1, L)).view(B, N)
-            dAs = ops.mul(dA, torch.full_like(dA, 1.0 / (N ** 0.5)))                               # A = softmax / sqrt(N)
-            ds = ops.softmax_rows_bwd(Asm, dAs).view(-1)
-            dT, dwb, dbb, dba = ops.gated_score_bwd(U, wb.reshape(-1).contiguous(), ds, gated=False)
-            dwb, dba = dwb.view(1, -1), dba.contiguous()
-        dwa = ops.gemm_tn(dT, h3)
-        if m3 is not None:
-            if ctx.pool_fast:
-                dz3, _, db3 = ops.panel_gemm(dT, wat, ops.PG_RANK1_MASK, bitmask=m3, rowscale=scores.view(-1), bias=ml, rank1=dM,
-                                             rows_per_bag=N, colsum=True, frag=False)
-            else:
-                dz3, _, db3 = ops.panel_gemm(dT, wat, ops.PG_RANK1_MASK, bitmask=m3, rowscale=A.view(-1), rank1=dM, rows_per_bag=N, colsum=True,
-                                             frag=False)
-            dz2, _, db2 = ops.panel_gemm(dz3, w3t, ops.PG_MASK, bitmask=m2, colsum=True, frag=fr)
-            dz1, _, db1 = ops.panel_gemm(dz2, w2t, ops.PG_MASK, bitmask=m1, colsum=True, frag=fr)
-        else:
-            dz3, ws = ops.gemm_nt(dT, wat, epi=ops.EPI_RANK1_MASK, mask=h3, rowscale=A.view(-1), rank1=dM, rows_per_bag=N, colsum=True)
-            db3 = ops.colsum(ws)
-            dz2, ws = ops.gemm_nt(dz3, w3t, epi=ops.EPI_MASK, mask=h2, colsum=True)
-            db2 = ops.colsum(ws)
-            dz1, ws = ops.gemm_nt(dz2, w2t, epi=ops.EPI_MASK, mask=h1, colsum=True)
-            db1 = ops.colsum(ws)
-        dw3, dw2, dw1 = ops.gemm_tn(dz3, h2), ops.gemm_tn(dz2, h1), ops.gemm_tn(dz1, x2)
-        dx = ops.gemm_nt(dz1, ops.transpose_cast(w1, T)).view(B, N, d) if ctx.needs_input_grad[0] else None
-        if ctx.drop_scale is not None:
-            # dZ2 = (dZ3 W3) * relu'(H2) * keep2 and dZ1 = (dZ2 W2) * relu'(H1) * keep1, the masks above hold relu' AND kept
-            s2 = ctx.drop_scale[1]
-            s1 = ctx.drop_scale[0] * s2
-            dw2, db2, dw1, db1 = dw2 * s2, db2 * s2, dw1 * s1, db1 * s1
-            dx = dx * s1 if dx is not None else None
-        return dx, dw1, db1, dw2, db2, dw3, db3, dwa, dba, dwb, dbb, dwd, dbd, None
+        return _abmil_backward(ctx.saved_tensors, ctx.dims, dout, ctx.needs_input_grad[0], ctx.wfrag, pool_fast=ctx.pool_fast,
+                               drop_scale=ctx.drop_scale) + (None, None)
 
 
 def attention_rows(att, stats):
@@ -642,7 +610,6 @@ class ABMILStepFn(torch.autograd.Function):
     def forward(ctx, x, w1, b1, w2, b2, w3, b3, wa, ba, wb, bb, wd, bd, session):
         s, t = session, session.t
         B, N, d = x.shape
-        T = x.dtype
         if not (t < s.steps and (B, N, d) == (s.bags, s.N, s.d)):
             # (a session left behind by a step that raised: drop it rather than trip every later call)
             raise RuntimeError("EncoderSession: shape / step count differ from what it was built for - a previous step may have "
@@ -650,19 +617,12 @@ class ABMILStepFn(torch.autograd.Function):
         x2 = s.x[t].view(B * N, d)
         if x.data_ptr() != x2.data_ptr():
             x2.copy_(x.reshape(B * N, d))
-        w1c, w2c, w3c, wac, wat, w3t, w2t = ops.weight_views(_frag_specs(w1, w2, w3, wa, T) if _FRAG_WEIGHTS else
-                                                             [(w, False, T) for w in (w1, w2, w3, wa)] +
-                                                             [(wa, True, T), (w3, True, T), (w2, True, T)])
-        nt = _STREAM_A
-        h1, _, _ = ops.panel_gemm(x2, w1c, ops.PG_BIAS_RELU, bias=b1, want_bitmask=True, stream_a=bool(nt & 1),
-                                  out=s.rows(s.h1, t), bitmask_out=s.rows(s.m1, t))
-        h2, _, _ = ops.panel_gemm(h1, w2c, ops.PG_BIAS_RELU, bias=b2, want_bitmask=True, reverse=True, stream_a=bool(nt & 2),
-                                  out=s.rows(s.h2, t), bitmask_out=s.rows(s.m2, t))
-        h3, _, _ = ops.panel_gemm(h2, w3c, ops.PG_BIAS_RELU, bias=b3, want_bitmask=True, stream_a=bool(nt & 4),
-                                  out=s.rows(s.h3, t), bitmask_out=s.rows(s.m3, t))
         blk = lambda buf: s.rows(buf, t, B)                                          # noqa: E731
-        scores, part = ops.abmil_pool_partials(h3.view(B, N, s.L), wac, ba, wb, bb, scores=blk(s.scores))
-        out, _, ml = ops.abmil_pool_decoder(part, B, N, T, wd, bd, out=(blk(s.out), blk(s.M), blk(s.ml)))
+        blocks = (s.rows(s.h1, t), s.rows(s.h2, t), s.rows(s.h3, t), s.rows(s.m1, t), s.rows(s.m2, t), s.rows(s.m3, t),
+                  blk(s.scores), (blk(s.out), blk(s.M), blk(s.ml)))
+        _h1, _h2, _h3, _m1, _m2, _m3, scores, _M, ml, out, views = _abmil_fast_forward(
+            x2, B, N, (w1, b1, w2, b2, w3, b3, wa, ba, wb, bb, wd, bd), blocks=blocks)
+        wac, wat, w3t, w2t = views[3:]
         s.weights = (w1, w2, w3, wa, ba, wb, wd, wac, b1, b2, b3, bb, bd, wat, w3t, w2t)
         s.wfrag = ops.is_frag(wac)
         s.t, s.pending = t + 1, s.pending + 1
@@ -693,7 +653,7 @@ class ABMILStepFn(torch.autograd.Function):
         R, Bt = n * s.bags * s.N, n * s.bags
         saved = (s.x.view(-1, s.d)[:R], s.h1[:R], s.h2[:R], s.h3[:R], s.scores[:Bt], None, s.M[:Bt], s.ml[:Bt], s.out[:Bt],
                  w1, w2, w3, wa, ba, wb, wd, wac, s.m1[:R], s.m2[:R], s.m3[:R], b1, b2, b3, bb, bd, wat, w3t, w2t)
-        return ABMILFn._backward_default(saved, (Bt, s.N, s.d), dout_all, False, s.wfrag) + (None,)
+        return _abmil_backward(saved, (Bt, s.N, s.d), dout_all, False, s.wfrag, pool_fast=True, drop_scale=None) + (None,)
 
 
 class SessionOutFn(torch.autograd.Function):
