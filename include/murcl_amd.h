@@ -396,10 +396,8 @@ int murcl_relu_bwd(const float* dy, const float* y, float* dx, long n, murcl_str
  * shared by all B rows (zero initial state: gh = b_hh, no [B,3H] copy of the bias). */
 int murcl_gru_gates_fwd(const float* gi, const float* gh, const float* hprev, float* hnew, float* gates, int B, int H,
                         int gh_bcast, murcl_stream_t stream);
-int murcl_gru_gates_bwd(const float* dh, const float* gates, const float* gh, const float* hprev, float* dgi,
-                        float* dgh, float* dhprev, int B, int H, int gh_bcast, murcl_stream_t stream);
-/* the same; accumulate != 0: dhprev += dh * z (back-propagation through time, where dhprev already holds that step's own
- * upstream gradient) */
+/* the gate backward: dgi, dgh [B,3H] and dhprev [B,H] (may be NULL) = dh * z; accumulate != 0: dhprev += dh * z (back-propagation
+ * through time, where dhprev already holds that step's own upstream gradient) */
 int murcl_gru_gates_bwd_into(const float* dh, const float* gates, const float* gh, const float* hprev, float* dgi,
                              float* dgh, float* dhprev, int B, int H, int gh_bcast, int accumulate, murcl_stream_t stream);
 

@@ -95,7 +95,6 @@ SIGNATURES = {
     "murcl_colsum": [_P, _P, _I, _I, _I, _I, _I, _P],
     "murcl_relu_bwd": [_P, _P, _P, _L, _P],
     "murcl_gru_gates_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
-    "murcl_gru_gates_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "murcl_gru_gates_bwd_into": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "murcl_gru_step_supported": [_I, _I, _I],
     "murcl_gru_step_fwd": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],

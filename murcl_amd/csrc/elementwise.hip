@@ -453,14 +453,7 @@ extern "C" int murcl_gru_gates_fwd(const float* gi, const float* gh, const float
     hipLaunchKernelGGL(gru_gates_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, gi, gh, hprev, hnew, gates, B, H, gh_bcast);
     return MURCL_CHECK_LAUNCH();
 }
-extern "C" int murcl_gru_gates_bwd(const float* dh, const float* gates, const float* gh, const float* hprev, float* dgi,
-                                   float* dgh, float* dhprev, int B, int H, int gh_bcast, hipStream_t s) {
-    const long n = (long)B * H;
-    if (n <= 0) return 0;
-    hipLaunchKernelGGL(gru_gates_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dh, gates, gh, hprev, dgi, dgh, dhprev, B, H, gh_bcast, 0);
-    return MURCL_CHECK_LAUNCH();
-}
-// the same with dhprev += dh * z when accumulate != 0 (backward through time: dhprev already holds the step's own upstream)
+// dhprev = dh * z, or += when accumulate != 0 (backward through time: dhprev already holds the step's own upstream)
 extern "C" int murcl_gru_gates_bwd_into(const float* dh, const float* gates, const float* gh, const float* hprev, float* dgi,
                                         float* dgh, float* dhprev, int B, int H, int gh_bcast, int accumulate, hipStream_t s) {
     const long n = (long)B * H;

@@ -690,169 +690,147 @@ def session_whole(session, hs):
     return SessionOutFn.apply(session, *hs)
 
 
-class GRUStepFn(torch.autograd.Function):
-    """One nn.GRU time step (seq_len 1, PyTorch gate order); h_prev None == zeros."""
-
-    @staticmethod
-    def forward(ctx, x, h_prev, w_ih, w_hh, b_ih, b_hh):
-        x = x.contiguous()
-        if h_prev is None and x.dtype == torch.float32 and ops.gru_step_ok(x.shape[0], w_hh.shape[1], x.shape[1]):
-            # restart: the input product and the gates in one launch (h W_hh^T = 0, gh = b_hh)
-            h_new, gates, _ = ops.gru_step_fwd(b_ih.detach(), None, w_hh.detach(), b_hh.detach(), x=x, w_ih=w_ih.detach(), want_gh=False)
-            ctx.save_for_backward(x, None, w_ih, w_hh, gates, b_hh.detach().view(1, -1), b_ih, b_hh)
-            return h_new
-        gi = ops.gemm_nt(x, w_ih, epi=ops.EPI_BIAS, bias=b_ih)
-        if h_prev is None:
-            gh = b_hh.detach().view(1, -1)                                   # W_hh . 0 + b_hh: one row, read by every batch row
+def _gru_forward(x2, B, zero_blocks, w_ih, w_hh, b_ih, b_hh, *, h_prev=None, step=False, keep=True):
+    """nn.GRU (PyTorch gate order) over x2 [n*B, I] f32 = n blocks of B rows: the first ``zero_blocks`` blocks start from the zero state,
+    block k >= ``zero_blocks`` continues from block k-1 - or, a single block with ``zero_blocks`` = 0, from the external ``h_prev`` [B,H].
+    The layouts: one step (n = 1), nn.GRU over a rollout (T blocks, 1 from zero), the 2T aggregator outputs of a contrastive step
+    x_00, x_01, x_10, x_11, ... (2 from zero: ``restart`` at patch step 0, then the reference's one shared hidden state).
+    ``step``: a single cell, whose input product joins the gate launch where the kernel takes it; every other layout forms the input
+    projection of all rows as ONE GEMM.  ``keep``: also produce what ``_gru_backward`` reads.
+    -> (hs [n*B, H]: every hidden state in one buffer, gates [n*B, 3H], gh [n*B, 3H]); without ``keep`` the last two are None.
+    The zero-state rows of gh stay unwritten: W_hh . 0 + b_hh is ONE row, b_hh, that every such row reads."""
+    R, H = x2.shape[0], w_hh.shape[1]
+    n, z = R // B, zero_blocks
+    assert R == n * B and 0 <= z <= n and (h_prev is None) == (z > 0) and (h_prev is None or n == 1) and (not step or n == 1)
+    wih, whh, bih, bhh = w_ih.detach(), w_hh.detach(), b_ih.detach(), b_hh.detach()
+    if step and x2.dtype == torch.float32 and ops.gru_step_ok(B, H, x2.shape[1]) and (h_prev is None or not keep):
+        # both products of the cell (from the zero state: the input product) and the gate math in one launch; a continuing step
+        # that a backward pass may follow has always taken the chain below instead (gemm_nt + the one-launch step)
+        hs, gates, _ = ops.gru_step_fwd(bih, h_prev, whh, bhh, x=x2, w_ih=wih, want_backward=keep, want_gh=False)
+        return hs, gates, None
+    # h W_hh^T and the gate math of a continuing block in one launch, or gemm_nt + gate kernel.  (A forward-only step that the form
+    # above refused - an input width that is no multiple of 16 - has always taken the latter.)
+    fused = ops.gru_step_ok(B, H) and (keep or not step)
+    e = lambda cols, on=True: torch.empty((R, cols), dtype=torch.float32, device=x2.device) if on else None      # noqa: E731
+    blk = lambda t, k: None if t is None else t[k * B:(k + 1) * B]                                               # noqa: E731
+    gi = ops.gemm_nt(x2, wih, epi=ops.EPI_BIAS, bias=bih)
+    hs, gates, gh = e(H), e(3 * H, keep), e(3 * H, n > z and (keep or not fused))
+    if z:
+        ops.gru_gates_fwd(gi[:z * B], bhh.view(1, -1), None, hnew=hs[:z * B], gates=None if gates is None else gates[:z * B])
+    for k in range(z, n):
+        prev = blk(hs, k - 1) if k else h_prev
+        if fused:
+            ops.gru_step_fwd(blk(gi, k), prev, whh, bhh, hnew=blk(hs, k), gates=blk(gates, k), gh=blk(gh, k) if keep else None,
+                             want_backward=keep)
         else:
-            h_prev = h_prev.contiguous()
-            if ops.gru_step_ok(h_prev.shape[0], h_prev.shape[1]):            # product + gates in one launch
-                h_new, gates, gh = ops.gru_step_fwd(gi, h_prev, w_hh.detach(), b_hh.detach())
-                ctx.save_for_backward(x, h_prev, w_ih, w_hh, gates, gh, b_ih, b_hh)
-                return h_new
-            gh = ops.gemm_nt(h_prev, w_hh, epi=ops.EPI_BIAS, bias=b_hh)
-        h_new, gates = ops.gru_gates_fwd(gi, gh, h_prev)
-        ctx.save_for_backward(x, h_prev, w_ih, w_hh, gates, gh, b_ih, b_hh)
-        return h_new
-
-    @staticmethod
-    def backward(ctx, dh):
-        _enter(ctx)
-        x, h_prev, w_ih, w_hh, gates, gh, b_ih, b_hh = ctx.saved_tensors
-        dgi, dgh, dhp = ops.gru_gates_bwd(dh.contiguous(), gates, gh, h_prev)
-        dx = ops.gemm_nt(dgi, ops.transposed(w_ih)) if ctx.needs_input_grad[0] else None
-        dw_ih, db_ih = _wbgrad(dgi, x, w_ih, b_ih)
-        if h_prev is None:
-            db_hh = _bgrad(dgh, b_hh)
-            # nn.GRU from a zero state: a zero gradient, but a gradient (Adam applies decay) - announced here when direct, by
-            # AccumulateGrad's hook otherwise (and not at all when this backward pass does not accumulate into w_hh)
-            dh_prev, dw_hh = None, (_touch(w_hh) if _direct(w_hh) else torch.zeros_like(w_hh))
-        else:
-            dw_hh, db_hh = _wbgrad(dgh, h_prev, w_hh, b_hh)
-            dh_prev = None
-            if ctx.needs_input_grad[1]:
-                dh_prev = ops.gemm_nt(dgh, ops.transposed(w_hh), out=dhp, accumulate=True)
-        return dx, dh_prev, dw_ih, dw_hh, db_ih, db_hh
+            ops.gemm_nt(prev, whh, epi=ops.EPI_BIAS, bias=bhh, out=blk(gh, k))
+            ops.gru_gates_fwd(blk(gi, k), blk(gh, k), prev, hnew=blk(hs, k), gates=blk(gates, k))
+    return hs, gates, (gh if keep else None)
 
 
-class GRUSeqFn(torch.autograd.Function):
-    """nn.GRU over a whole rollout from a zero hidden state (ActorCritic.evaluate, models/rlmil.py:99-112).
-
-    x [T,B,I] -> all hidden states [T,B,H].  The input projection and every weight/bias gradient are one GEMM /
-    one column sum over the T*B rows; only h W_hh^T and the gate kernels stay inside the time loop.
-    """
-
-    @staticmethod
-    def forward(ctx, x, w_ih, w_hh, b_ih, b_hh):
-        T, B, _ = x.shape
-        H = w_hh.shape[1]
-        x2 = x.reshape(T * B, -1).contiguous()
-        gi = ops.gemm_nt(x2, w_ih, epi=ops.EPI_BIAS, bias=b_ih).view(T, B, 3 * H)
-        gh = torch.empty((T, B, 3 * H), dtype=torch.float32, device=x.device)
-        gates = torch.empty_like(gh)
-        hs = torch.empty((T, B, H), dtype=torch.float32, device=x.device)
-        fused = ops.gru_step_ok(B, H)                                    # h W_hh^T and the gate math of a step in one launch
-        whh, bhh = w_hh.detach(), b_hh.detach()
-        gh0 = bhh.view(1, -1)                                            # W_hh . 0 + b_hh: ONE row that every batch row of step 0 reads (gh[0] stays unwritten)
-        for t in range(T):
-            if t and fused:
-                ops.gru_step_fwd(gi[t], hs[t - 1], whh, bhh, hnew=hs[t], gates=gates[t], gh=gh[t])
-                continue
-            if t:
-                ops.gemm_nt(hs[t - 1], w_hh, epi=ops.EPI_BIAS, bias=b_hh, out=gh[t])
-            ops.gru_gates_fwd(gi[t], gh[t] if t else gh0, hs[t - 1] if t else None, hnew=hs[t], gates=gates[t])
-        ctx.save_for_backward(x2, w_ih, w_hh, gates, gh, hs, b_ih, b_hh)
-        return hs
-
-    @staticmethod
-    def backward(ctx, dhs):
-        _enter(ctx)
-        x2, w_ih, w_hh, gates, gh, hs, b_ih, b_hh = ctx.saved_tensors
-        T, B, H = hs.shape
-        dhs = dhs.contiguous()
-        dgi, dgh = torch.empty_like(gh), torch.empty_like(gh)
-        w_hh_t = ops.transposed(w_hh)
-        gh0 = b_hh.detach().view(1, -1)                                  # step 0's gh (see forward)
-        if T > 1 and ops.gru_step_ok(B, H):
-            # back through time, one launch per step: dh_{t-1} += dgh_t W_hh, then step t-1's gate backward on the finished rows;
-            # the working copy of the upstream gradients also collects the direct path dh_t * z_t of every step
-            work = ops.copy_flat(torch.empty_like(dhs), dhs)
-            ops.gru_gates_bwd_into(work[T - 1], gates[T - 1], gh[T - 1], hs[T - 2], dgi[T - 1], dgh[T - 1], work[T - 2], accumulate=True)
-            for t in range(T - 1, 0, -1):
-                ops.gru_step_bwd(dgh[t], w_hh_t, work[t - 1], gates[t - 1], gh[t - 1] if t > 1 else gh0, hs[t - 2] if t > 1 else None, dgi[t - 1],
-                                 dgh[t - 1], work[t - 2] if t > 1 else None, accumulate=True)
-        else:
-            carry = None
-            for t in range(T - 1, -1, -1):
-                dh = dhs[t] if carry is None else dhs[t] + carry
-                _, _, dhp = ops.gru_gates_bwd(dh, gates[t], gh[t] if t else gh0, hs[t - 1] if t else None, dgi=dgi[t], dgh=dgh[t])
-                if t:
-                    carry = ops.gemm_nt(dgh[t], w_hh_t, out=dhp, accumulate=True)
-        dgi2, dgh2 = dgi.view(T * B, 3 * H), dgh.view(T * B, 3 * H)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = ops.gemm_nt(dgi2, ops.transposed(w_ih)).view(T, B, -1)
-        dw_ih = _wgrad(dgi2, x2, w_ih)
-        if T > 1:
-            dw_hh = _wgrad(dgh2[B:], hs.view(T * B, H)[:-B], w_hh)
-        else:
-            dw_hh = _touch(w_hh) if _direct(w_hh) else torch.zeros_like(w_hh)        # (_touch returns None)
-        return dx, dw_ih, dw_hh, _bgrad(dgi2, b_ih), _bgrad(dgh2, b_hh)
-
-
-class GRUViewSeqFn(torch.autograd.Function):
-    """The recurrent head over the n = 2T aggregator outputs of a contrastive step as ONE node (Full_layer.forward_view_sequence;
-    train_MuRCL.py:243,272 with the reference's one shared hidden state): x [n*B, F] = the blocks x_00, x_01, x_10, x_11, ... of B rows;
-    blocks 0 and 1 start from the zero state (``restart`` at patch step 0), block k >= 2 continues from block k-1 -> every hidden
-    state [n*B, H] in one buffer.  The input projection, the input gradient and each weight / bias gradient are ONE launch over all
-    n*B rows; no slice of x enters the graph (slicing x into a single step and a sequence cost two zero-fills, two copies and an
-    add in the backward pass, and a concatenation of the two results in the forward pass).  Needs n >= 3 and the one-launch step
-    kernels (``ops.gru_step_ok``)."""
-
-    @staticmethod
-    def forward(ctx, x, B, w_ih, w_hh, b_ih, b_hh):
-        x2 = x.contiguous()
-        R, H = x2.shape[0], w_hh.shape[1]
-        n = R // B
-        assert R == n * B and n >= 3 and ops.gru_step_ok(B, H)
-        gi = ops.gemm_nt(x2, w_ih, epi=ops.EPI_BIAS, bias=b_ih)                      # [R, 3H]
-        gh = torch.empty((R, 3 * H), dtype=torch.float32, device=x.device)          # (blocks 0 and 1 stay unwritten: they read the bias row)
-        gates = torch.empty_like(gh)
-        hs = torch.empty((R, H), dtype=torch.float32, device=x.device)
-        whh, bhh = w_hh.detach(), b_hh.detach()
-        ops.gru_gates_fwd(gi[:2 * B], bhh.view(1, -1), None, hnew=hs[:2 * B], gates=gates[:2 * B])     # both zero-state blocks: one launch
-        for k in range(2, n):
-            lo, hi = k * B, (k + 1) * B
-            ops.gru_step_fwd(gi[lo:hi], hs[lo - B:lo], whh, bhh, hnew=hs[lo:hi], gates=gates[lo:hi], gh=gh[lo:hi])
-        ctx.save_for_backward(x2, w_ih, w_hh, gates, gh, hs, b_ih, b_hh)
-        ctx.B = B
-        return hs
-
-    @staticmethod
-    def backward(ctx, dhs):
-        _enter(ctx)
-        x2, w_ih, w_hh, gates, gh, hs, b_ih, b_hh = ctx.saved_tensors
-        B = ctx.B
-        R, H = hs.shape
-        n = R // B
-        blk = lambda t, k: t[k * B:(k + 1) * B]                                       # noqa: E731
-        dgi, dgh = torch.empty_like(gh), torch.empty_like(gh)
-        w_hh_t = ops.transposed(w_hh)
-        gh0 = b_hh.detach().view(1, -1)
-        # back through time on a working copy of the upstream gradients (it collects dh_t * z_t and dgh_{t+1} W_hh of every step)
-        work = ops.copy_flat(torch.empty((R, H), dtype=torch.float32, device=hs.device), dhs.contiguous())
+def _gru_backward(gates, gh, hs, h_prev, gh0, B, zero_blocks, dhs, w_hh_t):
+    """Back through the blocks of ``_gru_forward`` (what it kept; ``gh0`` = b_hh as one row; ``dhs`` [n*B, H] contiguous; ``w_hh_t`` =
+    W_hh^T, not read for a single block) -> (dgi, dgh [n*B, 3H], dhp): dhp [B,H] = the direct path dh * z into an external ``h_prev``,
+    to which the caller adds dgh W_hh; None without one."""
+    R, H = dhs.shape
+    n, z = R // B, zero_blocks
+    blk = lambda t, k: t[k * B:(k + 1) * B]                                              # noqa: E731
+    dgi = torch.empty((R, 3 * H), dtype=torch.float32, device=dhs.device)
+    dgh = torch.empty_like(dgi)
+    if n > max(z, 1) and ops.gru_step_ok(B, H):
+        # one launch per block: dh_{k-1} += dgh_k W_hh, then block k-1's gate backward on the finished rows; the working copy of the
+        # upstream gradients also collects the direct path dh_k * z_k of every block
+        work = ops.copy_flat(torch.empty_like(dhs), dhs)
         ops.gru_gates_bwd_into(blk(work, n - 1), blk(gates, n - 1), blk(gh, n - 1), blk(hs, n - 2), blk(dgi, n - 1), blk(dgh, n - 1),
                                blk(work, n - 2), accumulate=True)
-        for k in range(n - 1, 1, -1):             # block k's dgh is complete: dh_{k-1} += dgh_k W_hh, then block k-1's gate backward
-            first = k - 1 == 1                    # block 1 started from the zero state: bias row, no previous state to pass a gradient to
-            ops.gru_step_bwd(blk(dgh, k), w_hh_t, blk(work, k - 1), blk(gates, k - 1), gh0 if first else blk(gh, k - 1),
-                             None if first else blk(hs, k - 2), blk(dgi, k - 1), blk(dgh, k - 1), None if first else blk(work, k - 2),
+        for k in range(n - 1, z - 1, -1):
+            zero = k - 1 < z                  # block k-1 started from the zero state: the bias row, no previous state to pass a gradient to
+            ops.gru_step_bwd(blk(dgh, k), w_hh_t, blk(work, k - 1), blk(gates, k - 1), gh0 if zero else blk(gh, k - 1),
+                             None if zero else blk(hs, k - 2), blk(dgi, k - 1), blk(dgh, k - 1), None if zero else blk(work, k - 2),
                              accumulate=True)
-        ops.gru_gates_bwd_into(blk(work, 0), blk(gates, 0), gh0, None, blk(dgi, 0), blk(dgh, 0))      # block 0: a single step beside the chain
-        dx = ops.gemm_nt(dgi, ops.transposed(w_ih)) if ctx.needs_input_grad[0] else None
+        if z > 1:                             # the zero-state blocks nothing continued from: single steps beside the chain
+            rows = slice(0, (z - 1) * B)
+            ops.gru_gates_bwd_into(work[rows], gates[rows], gh0, None, dgi[rows], dgh[rows])
+        return dgi, dgh, None
+    carry = dhp = None
+    for k in range(n - 1, -1, -1):
+        cont = k >= z
+        dh = blk(dhs, k) if carry is None else blk(dhs, k) + carry
+        _, _, dhp = ops.gru_gates_bwd(dh, blk(gates, k), blk(gh, k) if cont else gh0, (blk(hs, k - 1) if k else h_prev) if cont else None,
+                                      dgi=blk(dgi, k), dgh=blk(dgh, k))
+        carry = ops.gemm_nt(blk(dgh, k), w_hh_t, out=dhp, accumulate=True) if cont and k else None
+    return dgi, dgh, (dhp if h_prev is not None else None)
+
+
+def _gru_param_grads(dgi, dgh, x2, hs, h_prev, B, zero_blocks, w_ih, w_hh, b_ih, b_hh, split_bias):
+    """-> (dw_ih, dw_hh, db_ih, db_hh) of a ``_gru_forward`` pass.  ``split_bias``: the input side as ``_wgrad`` + ``_bgrad`` (two
+    launches, never deferred - what the rollout layout has always run) instead of ``_wbgrad``."""
+    R, z = x2.shape[0], zero_blocks
+    db_ih = db_hh = None
+    if split_bias:
+        dw_ih = _wgrad(dgi, x2, w_ih)
+    else:
         dw_ih, db_ih = _wbgrad(dgi, x2, w_ih, b_ih)
-        dw_hh = _wgrad(dgh[2 * B:], hs[B:R - B], w_hh)                                 # blocks k >= 2 against the state of block k-1
-        return dx, None, dw_ih, dw_hh, db_ih, _bgrad(dgh, b_hh)
+    if h_prev is not None:
+        dw_hh, db_hh = _wbgrad(dgh, h_prev, w_hh, b_hh)
+    elif R > z * B:
+        dw_hh = _wgrad(dgh[z * B:], hs[(z - 1) * B:R - B], w_hh)          # blocks k >= z against the state of block k-1
+    else:
+        # nn.GRU from a zero state: a zero gradient, but a gradient (Adam applies decay) - announced here when direct, by
+        # AccumulateGrad's hook otherwise (and not at all when this backward pass does not accumulate into w_hh)
+        dw_hh = _touch(w_hh) if _direct(w_hh) else torch.zeros_like(w_hh)        # (_touch returns None)
+    if split_bias:
+        db_ih = _bgrad(dgi, b_ih)
+    if h_prev is None:
+        db_hh = _bgrad(dgh, b_hh)
+    return dw_ih, dw_hh, db_ih, db_hh
+
+
+class GRUFn(torch.autograd.Function):
+    """``_gru_forward`` over the row blocks of x [n*B, I] (or [n, B, I]) as ONE node -> every hidden state, in x's leading shape.  The
+    input projection, the input gradient and each weight / bias gradient are ONE launch over all n*B rows; only h W_hh^T and the gate
+    kernels stay inside the loop over blocks."""
+
+    @staticmethod
+    def forward(ctx, x, h_prev, w_ih, w_hh, b_ih, b_hh, B, zero_blocks, step, split_bias):
+        x2 = _flat2(x).contiguous()
+        h_prev = None if h_prev is None else h_prev.contiguous()
+        hs, gates, gh = _gru_forward(x2, B, zero_blocks, w_ih, w_hh, b_ih, b_hh, h_prev=h_prev, step=step)
+        ctx.save_for_backward(x2, h_prev, w_ih, w_hh, gates, gh, hs, b_ih, b_hh)
+        ctx.layout = (B, zero_blocks, step, split_bias, x.shape)
+        return hs if x.dim() == 2 else hs.view(*x.shape[:-1], hs.shape[1])
+
+    @staticmethod
+    def backward(ctx, dhs):
+        _enter(ctx)
+        x2, h_prev, w_ih, w_hh, gates, gh, hs, b_ih, b_hh = ctx.saved_tensors
+        B, z, step, split_bias, xshape = ctx.layout
+        # (every layout but the single step forms W_hh^T up front - a rollout of one block too, which does not read it)
+        w_hh_t = None if step else ops.transposed(w_hh)
+        dgi, dgh, dhp = _gru_backward(gates, gh, hs, h_prev, b_hh.detach().view(1, -1), B, z, _flat2(dhs).contiguous(), w_hh_t)
+        dx = ops.gemm_nt(dgi, ops.transposed(w_ih)).view(xshape) if ctx.needs_input_grad[0] else None
+        grads = _gru_param_grads(dgi, dgh, x2, hs, h_prev, B, z, w_ih, w_hh, b_ih, b_hh, split_bias)
+        dh_prev = None
+        if h_prev is not None and ctx.needs_input_grad[1]:
+            dh_prev = ops.gemm_nt(dgh, ops.transposed(w_hh), out=dhp, accumulate=True)
+        return (dx, dh_prev) + grads + (None,) * 4
+
+
+class GRUStepFn:
+    """One nn.GRU time step (seq_len 1); ``h_prev`` None == zeros."""
+
+    @staticmethod
+    def apply(x, h_prev, w_ih, w_hh, b_ih, b_hh):
+        return GRUFn.apply(x, h_prev, w_ih, w_hh, b_ih, b_hh, x.shape[0], int(h_prev is None), True, False)
+
+
+class GRUSeqFn:
+    """nn.GRU over a whole rollout from a zero hidden state (ActorCritic.evaluate, models/rlmil.py:99-112): x [T,B,I] -> all hidden
+    states [T,B,H]."""
+
+    @staticmethod
+    def apply(x, w_ih, w_hh, b_ih, b_hh):
+        return GRUFn.apply(x, None, w_ih, w_hh, b_ih, b_hh, x.shape[1], 1, False, True)
 
 
 class NTXentSeqFn(torch.autograd.Function):

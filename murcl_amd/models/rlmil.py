@@ -16,7 +16,7 @@ from torch import nn
 
 import math
 
-from ..functional import GRUSeqFn, GRUStepFn, LinearFn, PolicyHeadFn, PPOLossFn
+from ..functional import GRUFn, GRUSeqFn, GRUStepFn, LinearFn, PolicyHeadFn, PPOLossFn, _gru_forward
 from ..utils.views import whole as _whole
 
 
@@ -42,41 +42,31 @@ class Full_layer(nn.Module):
         self.hidden = None
         self.fc_rnn = fc_rnn
         if fc_rnn:
-            self.rnn = nn.GRU(feature_num, hidden_state_dim)      # parameter holder; math in GRUStepFn
+            self.rnn = nn.GRU(feature_num, hidden_state_dim)      # parameter holder; math in functional.GRUFn
             self.fc = nn.Linear(hidden_state_dim, class_num)
         else:
             for k in (2, 3, 4, 5):                                # cascaded variant (rlmil.py:203-206)
                 setattr(self, f"fc_{k}", nn.Linear(feature_num * k, class_num))
 
-    def _step_no_grad(self, x, h_prev):
-        """One GRU step + classifier with the kernels called directly (forward-only callers: frozen-encoder stage 2,
-        validation): no autograd nodes to build."""
-        from .. import ops
-        r = self.rnn
-        x = x.contiguous()
-        h_prev = None if h_prev is None else h_prev.contiguous()
-        if x.dtype == torch.float32 and ops.gru_step_ok(x.shape[0], self.hidden_state_dim, x.shape[1]):
-            # both products of the cell (from the zero state: the input product) and the gate math in one launch
-            h = ops.gru_step_fwd(r.bias_ih_l0.detach(), h_prev, r.weight_hh_l0.detach(), r.bias_hh_l0.detach(), x=x,
-                                 w_ih=r.weight_ih_l0.detach(), want_backward=False)[0]
-        else:
-            gi = ops.gemm_nt(x, r.weight_ih_l0, epi=ops.EPI_BIAS, bias=r.bias_ih_l0)
-            gh = r.bias_hh_l0.detach().view(1, -1) if h_prev is None else \
-                ops.gemm_nt(h_prev, r.weight_hh_l0, epi=ops.EPI_BIAS, bias=r.bias_hh_l0)
-            h = ops.gru_gates_fwd(gi, gh, h_prev)[0]
-        return h, ops.gemm_nt(h, self.fc.weight, epi=ops.EPI_BIAS, bias=self.fc.bias)
+    def _head(self, x, B, zero_blocks, h_prev=None, step=False):
+        """The GRU over the row blocks of x [n*B, F] (``functional._gru_forward``: blocks, zero state, ``step``), then the classifier
+        over all rows -> (hs [n*B, H], z [n*B, class_num]): ONE recurrent node and one Linear node - or, for forward-only callers
+        (frozen-encoder stage 2, validation), the same chain called directly: no autograd nodes to build, no tensors kept."""
+        r, fc = self.rnn, self.fc
+        p = (r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)
+        if not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2:
+            from .. import ops
+            h_prev = None if h_prev is None else h_prev.contiguous()
+            hs = _gru_forward(x.contiguous(), B, zero_blocks, *p, h_prev=h_prev, step=step, keep=False)[0]
+            return hs, ops.gemm_nt(hs, fc.weight.detach(), epi=ops.EPI_BIAS, bias=fc.bias.detach())
+        hs = GRUFn.apply(x, h_prev, *p, B, zero_blocks, step, False)
+        return hs, LinearFn.apply(hs, fc.weight, fc.bias, False)
 
     def forward(self, x, restart=False):
         if self.fc_rnn:
-            h_prev = None if restart else self.hidden[0]
-            if not torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2:
-                h, z = self._step_no_grad(x, h_prev)
-                self.hidden = h.unsqueeze(0)
-                return z
-            r = self.rnn
-            h = GRUStepFn.apply(x, h_prev, r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)
+            h, z = self._head(x, x.shape[0], int(restart), None if restart else self.hidden[0], step=True)
             self.hidden = h.unsqueeze(0)                          # [1,B,H] like nn.GRU's h_n
-            return LinearFn.apply(h, self.fc.weight, self.fc.bias, False)
+            return z
         self.hidden = x if restart else torch.cat([self.hidden, x], 1)
         k = self.hidden.size(1) // self.feature_num
         if k == 1:
@@ -86,14 +76,12 @@ class Full_layer(nn.Module):
         head = getattr(self, f"fc_{k}")
         return LinearFn.apply(self.hidden, head.weight, head.bias, False)
 
-
     def forward_sequence(self, x):
         """x [T,B,F]: ``[self(x[t], restart=(t == 0)) for t in range(T)]`` as ONE recurrent node and one classifier product over
         the T*B rows -> logits [T*B, class_num]; ``self.hidden`` ends as after the loop.  (The supervised step computes all T
         sub-bags of a stage-1 step before the head runs, so the head needs no per-step launches from Python.)"""
         if not self.fc_rnn:
             return torch.cat([self(x[t], restart=(t == 0)) for t in range(x.shape[0])], 0)
-        from ..functional import GRUSeqFn
         r = self.rnn
         hs = GRUSeqFn.apply(x.float(), r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)
         self.hidden = hs[-1].unsqueeze(0)
@@ -104,45 +92,29 @@ class Full_layer(nn.Module):
         (2T tensors [B,F]) -> z [2T*B, class_num] in the same order, as if
         ``forward_views([x_t0, x_t1], restart=(t == 0))`` had been called step by step (train_MuRCL.py:243,272).  With the one
         shared hidden state of the reference that loop is ONE chain: both views of step 0 start from zero, then
-        h(0,1) -> h(1,0) -> h(1,1) -> h(2,0) -> ...; so x_01, x_10, x_11, ... run as one recurrent node from a zero state and
-        x_00 as a single step beside it, and the classifier is one product over the 2T*B rows."""
+        h(0,1) -> h(1,0) -> h(1,1) -> h(2,0) -> ...: one recurrent node over the 2T blocks with two zero-state blocks, every hidden
+        state in one buffer, and the classifier one product over the 2T*B rows.  No slice of x enters the graph (slicing x into a
+        single step and a sequence cost two zero-fills, two copies and an add in the backward pass, and a concatenation forward)."""
         if not self.fc_rnn:
             raise RuntimeError("forward_view_sequence needs the recurrent head (fc_rnn=True)")
-        from ..functional import GRUSeqFn
+        from .. import ops
         xs = list(xs)
-        n2, B = len(xs), xs[0].shape[0]
-        x = whole if whole is not None else (_whole(xs) if n2 > 1 else xs[0])        # ``whole``: torch.cat(xs, 0), already in one tensor
+        n2, B, x0 = len(xs), xs[0].shape[0], xs[0]
+        x = whole if whole is not None else (_whole(xs) if n2 > 1 else x0)            # ``whole``: torch.cat(xs, 0), already in one tensor
         assert whole is None or (whole.dim() == 2 and whole.shape[0] == n2 * B)
-        r = self.rnn
-        if (not torch.is_grad_enabled() and xs[0].is_cuda and xs[0].dtype == torch.float32 and xs[0].dim() == 2 and n2 > 1
-                and len({tuple(t.shape) for t in xs}) == 1):
-            from .. import ops
-            H = r.weight_hh_l0.shape[1]
-            if ops.gru_step_ok(B, H) and n2 >= 3:
-                # nobody differentiates this pass (frozen-aggregator stage 2, validation): the launches of GRUViewSeqFn.forward without
-                # the tensors its backward pass would need - one stacking launch, one input product over all rows, every hidden state
-                # written straight into the rows of ONE buffer
-                if x is None:
-                    x = ops.stack_lists([xs])[0].view(n2 * B, -1)
-                wih, whh, bih, bhh = (t.detach() for t in (r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0))
-                h_all = torch.empty((n2 * B, H), dtype=torch.float32, device=x.device)
-                gi = ops.gemm_nt(x, wih, epi=ops.EPI_BIAS, bias=bih)
-                ops.gru_gates_fwd(gi[:2 * B], bhh.view(1, -1), None, hnew=h_all[:2 * B])          # blocks 0 and 1: from the zero state
-                for k in range(2, n2):
-                    ops.gru_step_fwd(gi[k * B:(k + 1) * B], h_all[(k - 1) * B:k * B], whh, bhh, hnew=h_all[k * B:(k + 1) * B],
-                                     want_backward=False)
-                self.hidden = h_all[-B:].unsqueeze(0)
-                return ops.gemm_nt(h_all, self.fc.weight.detach(), epi=ops.EPI_BIAS, bias=self.fc.bias.detach())
+        one_node = n2 >= 3 and x0.is_cuda and x0.dim() == 2 and ops.gru_step_ok(B, self.hidden_state_dim)
         if x is None:
-            x = torch.cat(xs, 0)
+            if (one_node and not torch.is_grad_enabled() and x0.dtype == torch.float32 and len({tuple(t.shape) for t in xs}) == 1):
+                x = ops.stack_lists([xs])[0].view(n2 * B, -1)                         # forward only: one stacking launch of our own
+            else:
+                x = torch.cat(xs, 0)
         x = x.float()
-        if n2 >= 3 and x.is_cuda and x.dim() == 2:
-            from .. import ops
-            from ..functional import GRUViewSeqFn
-            if ops.gru_step_ok(B, r.weight_hh_l0.shape[1]):
-                h_all = GRUViewSeqFn.apply(x, B, r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)      # one node, one buffer
-                self.hidden = h_all[-B:].unsqueeze(0)
-                return LinearFn.apply(h_all, self.fc.weight, self.fc.bias, False)
+        if one_node:
+            hs, z = self._head(x, B, 2)
+            self.hidden = hs[-B:].unsqueeze(0)
+            return z
+        # two blocks, or a shape the one-launch step kernels refuse: x_00 as a single step beside a rollout over the rest
+        r = self.rnn
         h00 = GRUStepFn.apply(x[:B], None, r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)
         hs = GRUSeqFn.apply(x[B:].view(n2 - 1, B, -1), r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)
         self.hidden = hs[-1].unsqueeze(0)
@@ -159,16 +131,11 @@ class Full_layer(nn.Module):
         if not (self.fc_rnn and restart and len(xs) > 1 and len({tuple(x.shape) for x in xs}) == 1):
             return [self(x, restart) for x in xs]
         n = xs[0].shape[0]
-        r = self.rnn
-        if not torch.is_grad_enabled() and xs[0].is_cuda and xs[0].dtype == torch.float32 and xs[0].dim() == 2:
-            x = _whole(xs)
-            h, z = self._step_no_grad(torch.cat(xs, 0) if x is None else x, None)
-            self.hidden = h[-n:].unsqueeze(0)
-            return list(z.split(n, 0))
         x = _whole(xs)
-        h = GRUStepFn.apply(torch.cat(xs, 0) if x is None else x, None, r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0)
+        x = torch.cat(xs, 0) if x is None else x
+        h, z = self._head(x, x.shape[0], 1, step=True)
         self.hidden = h[-n:].unsqueeze(0)
-        return list(LinearFn.apply(h, self.fc.weight, self.fc.bias, False).split(n, 0))
+        return list(z.split(n, 0))
 
 
 class ActorCritic(nn.Module):

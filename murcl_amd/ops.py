@@ -938,8 +938,8 @@ def gru_gates_bwd(dh, gates, gh, hprev, dgi=None, dgh=None):
         dgh = torch.empty((B, 3 * H), dtype=torch.float32, device=dh.device)
     assert dgi.is_contiguous() and dgh.is_contiguous() and gates.is_contiguous() and gh.is_contiguous()
     dhp = torch.empty((B, H), dtype=torch.float32, device=dh.device)
-    check(_lib.lib().murcl_gru_gates_bwd(ptr(dh), ptr(gates), ptr(gh), ptr(hprev), ptr(dgi), ptr(dgh), ptr(dhp), B, H,
-                                         int(gh.shape[0] == 1 and B != 1), stream()), "gru_gates_bwd")
+    check(_lib.lib().murcl_gru_gates_bwd_into(ptr(dh), ptr(gates), ptr(gh), ptr(hprev), ptr(dgi), ptr(dgh), ptr(dhp), B, H,
+                                              int(gh.shape[0] == 1 and B != 1), 0, stream()), "gru_gates_bwd")
     return dgi, dgh, dhp
 
 

@@ -57,6 +57,9 @@ class _FlatOptimizer:
             for name in self.STATE:
                 grp[name] = torch.zeros_like(flat_p)
             self.groups.append(grp)
+        # nothing has written into the gradients seated above: an id left in ``_TOUCHED`` by a parameter that was touched and never
+        # stepped (its optimizer dropped, the object freed, CPython handing its address to one of ours) is not ours
+        functional._TOUCHED -= self._ids
 
     @property
     def param_groups(self):            # lr schedulers poke group['lr']

@@ -388,6 +388,45 @@ def _gru_oracle(seed):
     return oracle
 
 
+# -- Full_layer over row blocks as one recurrent node: a rollout (forward_sequence) and the view sequence of a contrastive step
+def _gru_blocks_inputs(seed, n):
+    def inputs():
+        x = T(detrand.normal(seed, f"gb.x{n}", (n * 8, 512))).to(_dev()).requires_grad_()
+        return x, T(detrand.normal(seed, f"gb.w{n}", (n * 8, 128))).to(_dev())
+    return inputs
+
+
+def _gru_seq_fwd(m, inp):
+    x, w = inp
+    z = m.forward_sequence(x.view(-1, 8, 512))
+    return (z * w).sum(), z
+
+
+def _gru_view_seq_fwd(m, inp):
+    x, w = inp
+    z = m.forward_view_sequence(list(x.split(8, 0)))
+    return (z * w).sum(), z
+
+
+def _gru_blocks_oracle(seed, n, zero_blocks):
+    """``O.full_layer_step`` block by block: the first ``zero_blocks`` from the zero state, block k from block k-1."""
+    def oracle(case, got_out, got, got_x):
+        fp = {k: v.clone().requires_grad_() for k, v in P.to_torch(P.full_layer(seed)).items()}
+        x, w = (t.detach().cpu() for t in case.inputs())
+        x.requires_grad_()
+        zs, h = [], None
+        for k in range(n):
+            z, h = O.full_layer_step(fp, x[k * 8:(k + 1) * 8], None if k < zero_blocks else h)
+            zs.append(z)
+        z = torch.cat(zs)
+        (z * w).sum().backward()
+        _check_f32(got_out, z, "z", rtol=1e-4, atol=1e-5)
+        _check_f32(got_x, x.grad, "dx")
+        for k, v in got.items():
+            _check_f32(v, fp[k].grad, k)
+    return oracle
+
+
 CASES = {c.name: c for c in [
     _abmil_case("abmil_f32", 2, 300),
     # the bf16 fast path: d = L = 512, D = 128 at a row count the weight-stationary kernels take -> fragment-order weight views
@@ -404,6 +443,10 @@ CASES = {c.name: c for c in [
     _dsmil_case("dsmil_bf16_dropout_v", BF16),
     Case("cl_ntxent", _cl_build(), _cl_inputs(4, 256, 985), _cl_fwd, lambda inp: inp[0], _cl_oracle(985), seed=985),
     Case("full_layer_gru", _gru_build(13), _gru_inputs(13), _gru_fwd, lambda inp: inp[0], _gru_oracle(13), seed=13),
+    Case("full_layer_seq", _gru_build(14), _gru_blocks_inputs(14, 3), _gru_seq_fwd, lambda inp: inp[0], _gru_blocks_oracle(14, 3, 1),
+         seed=14),
+    Case("full_layer_view_seq", _gru_build(15), _gru_blocks_inputs(15, 6), _gru_view_seq_fwd, lambda inp: inp[0],
+         _gru_blocks_oracle(15, 6, 2), seed=15),
 ]}
 NAMES = list(CASES)
 HAS_DROPOUT = {"abmil_dropout_f32", "abmil_dropout_bf16", "clam_f32_dropout", "clam_bf16_dropout", "dsmil_f32_dropout_v",

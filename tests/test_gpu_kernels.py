@@ -1120,26 +1120,47 @@ def test_gru_step_backward_in_one_launch(B, H, first):
     _close(dprev, (0 if first else dprev0.double()) + d * z, rtol=1e-4, atol=2e-5)
 
 
-@pytest.mark.parametrize("T,B,I,H", [(6, 64, 512, 512), (3, 9, 48, 32), (1, 4, 32, 32)])
-def test_gru_sequence_function_against_torch_gru(T, B, I, H):
-    """functional.GRUSeqFn (one launch per time step and direction) against torch.nn.GRU on the CPU: all hidden states and
-    every gradient."""
-    from murcl_amd.functional import GRUSeqFn
+@pytest.mark.parametrize("layout,T,B,I,H", [
+    pytest.param("seq", 6, 64, 512, 512, id="6-64-512-512"), pytest.param("seq", 3, 9, 48, 32, id="3-9-48-32"),
+    pytest.param("seq", 1, 4, 32, 32, id="1-4-32-32"),
+    # gemm_nt + gate kernel per step (what an H that is no multiple of 16 takes), forced at a shape the generic kernels are tested on
+    pytest.param("seq", 3, 9, 48, 32, id="unfused-3-9-48-32"), pytest.param("pair", 2, 8, 32, 32, id="unfused-pair-8-32-32"),
+    pytest.param("views", 3, 8, 32, 32, id="views-3-8-32-32")])
+def test_gru_sequence_function_against_torch_gru(layout, T, B, I, H, request, monkeypatch):
+    """The layouts of functional.GRUFn against torch.nn.GRU in float64 on the CPU, all hidden states and every gradient: "seq" =
+    GRUSeqFn over a rollout from the zero state; "pair" = GRUStepFn from the zero state, then a continuing GRUStepFn; "views" = the
+    view sequence (blocks 0 and 1 from the zero state, block k from block k-1: the reference is chained by hand)."""
+    from murcl_amd import ops
+    from murcl_amd.functional import GRUFn, GRUSeqFn, GRUStepFn
     dev = _dev()
+    if request.node.callspec.id.startswith("unfused"):
+        monkeypatch.setattr(ops, "gru_step_ok", lambda *a, **k: False)
     torch.manual_seed(7)
     ref = torch.nn.GRU(I, H)
-    x = _rand(43, "x", (T, B, I)).requires_grad_()
+    names = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+    ps = [getattr(ref, k).detach().to(dev).requires_grad_() for k in names]
+    ref = ref.double()
+    x = _rand(43, "x", (T, B, I)).double().requires_grad_()
     dhs = _rand(43, "dhs", (T, B, H))
-    out, _ = ref(x)
-    (out * dhs).sum().backward()
-    ps = [p.detach().to(dev).requires_grad_() for p in (ref.weight_ih_l0, ref.weight_hh_l0, ref.bias_ih_l0, ref.bias_hh_l0)]
-    xd = x.detach().to(dev).requires_grad_()
-    hs = GRUSeqFn.apply(xd, *ps)
+    zero_blocks = 2 if layout == "views" else 1
+    outs = []
+    for k in range(T):
+        outs.append(ref(x[k:k + 1], None if k < zero_blocks else outs[-1])[0])
+    out = torch.cat(outs, 0)
+    (out * dhs.double()).sum().backward()
+    xd = x.detach().float().to(dev).requires_grad_()
+    if layout == "seq":
+        hs = GRUSeqFn.apply(xd, *ps)
+    elif layout == "pair":
+        h0 = GRUStepFn.apply(xd[0], None, *ps)
+        hs = torch.stack([h0, GRUStepFn.apply(xd[1], h0, *ps)], 0)
+    else:
+        hs = GRUFn.apply(xd.view(T * B, I), None, *ps, B, 2, False, False).view(T, B, H)
     (hs * dhs.to(dev)).sum().backward()
     _close(hs, out, rtol=1e-4, atol=2e-5)
     _close(xd.grad, x.grad, rtol=1e-3, atol=5e-5)
-    for p, q in zip(ps, (ref.weight_ih_l0, ref.weight_hh_l0, ref.bias_ih_l0, ref.bias_hh_l0)):
-        _close(p.grad, q.grad, rtol=1e-3, atol=2e-4)
+    for p, k in zip(ps, names):
+        _close(p.grad, getattr(ref, k).grad, rtol=1e-3, atol=2e-4)
 
 
 def test_adam_matches_oracle():

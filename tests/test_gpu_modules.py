@@ -387,7 +387,7 @@ def test_full_layer_view_sequence_without_grad_equals_the_per_step_loop_and_the_
 
 @pytest.mark.parametrize("whole", [True, False])
 def test_full_layer_view_sequence_node_equals_the_per_step_loop_with_gradients(whole):
-    """forward_view_sequence under grad = ONE recurrent node over the 2T blocks (functional.GRUViewSeqFn: one input product, one input
+    """forward_view_sequence under grad = ONE recurrent node over the 2T blocks (functional.GRUFn: one input product, one input
     gradient, one weight / bias gradient launch each over all rows; blocks 0 and 1 from the zero state): outputs, the gradient that
     reaches every aggregator output and every parameter gradient equal the reference's per-step loop
     `[fc(x, restart=(t == 0)) for x in views]` (train_MuRCL.py:243,272), for row blocks of one tensor and for separate tensors; the step

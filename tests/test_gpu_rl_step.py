@@ -251,6 +251,23 @@ def test_flat_adam_skips_parameters_without_gradient_like_torch():
             assert mine[2].grad.abs().max().item() == 0.0
 
 
+def test_flat_adam_ignores_touches_older_than_itself():
+    """``functional._TOUCHED`` holds ``id()``s: one left behind by a parameter that was touched and never stepped may be the address
+    of a parameter created later.  A new optimizer's parameters have no gradient yet, whatever the set says: without a backward
+    pass its step skips them (no weight decay, no moments), as torch's does for ``grad is None``."""
+    from murcl_amd import functional
+    from murcl_amd.optim import FlatAdam
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    p = torch.nn.Parameter(torch.randn(4, 16, device=dev))
+    before = p.detach().clone()
+    functional._touch(p)                                           # what a freed parameter at this address would have left
+    opt = FlatAdam([{"params": [p], "lr": 1e-2}], weight_decay=1e-2)
+    assert id(p) not in functional._TOUCHED
+    opt.step()
+    assert torch.equal(p.detach(), before)
+
+
 @pytest.mark.parametrize("momentum,nesterov", [(0.0, False), (0.9, False), (0.9, True)])
 def test_flat_sgd_equals_torch_sgd(momentum, nesterov):
     """--optimizer SGD (train_MuRCL.py:158-163): momentum buffer seeded by the first gradient, optional Nesterov, L2 decay."""
