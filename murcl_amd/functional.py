@@ -4,7 +4,9 @@ Forward and backward are sequences of C-ABI launches (murcl_amd.ops); torch supp
 only tensor storage and the autograd graph.  No CPU / eager-PyTorch fallback exists:
 CPU tensors raise.
 """
+import collections
 import contextlib
+import functools
 import math
 
 import torch
@@ -42,10 +44,6 @@ _FUSED_GATE = True        # CLAM, forward-only calls: the gate score from the ga
 _GATE_U = True            # CLAM, training chain: score + pre-activations from one gate GEMM, one-pass gate backward
 _FUSED_FC_DROP = True     # CLAM: the seeded Dropout behind the first layer's ReLU inside that GEMM's epilogue
 _FUSED_INST = True        # CLAM: the instance branch as one launch forward, one backward
-_DSMIL_REASSOC = True     # DSMIL: attention logits as X . (Wq^T q_max) - no GEMM over all patches (C <= 4)
-_DSMIL_ONEPASS = True     # ... with attention + pooling, and their backward, in one pass over X each
-_DSMIL_QV = True          # ... and the [B*C]-row algebra around them as three launches
-_DSMIL_X3 = True          # DSMIL's long f32 GEMMs (the literal-order chain) as a 3-term bf16 split
 _GROUP_WGRAD = True       # the encoder weight gradients of a backward pass as one grouped launch
 _FOLD_BIAS = True         # encoder bias gradients folded into the wgrad reduce
 _FRAG_WEIGHTS = True      # ABMIL bf16 fast path: the K = 512 weight operands as FRAGMENT-ORDER views (ops.is_frag; round 6)
@@ -572,6 +570,18 @@ def abmil_fast_path(rows, N, d, L, D, dtype):
             and ops.panel_supported(rows, L, 128, ops.PG_RANK1_MASK, N))
 
 
+DSMILRoute = collections.namedtuple("DSMILRoute", "reassoc qv stream")
+
+
+@functools.lru_cache(maxsize=None)
+def dsmil_route(B, N, d, C, dropped):
+    """Which chain a DSMIL call of this shape takes (``DSMILFn`` describes them); ``dropped``: the value branch's input has its own dropout."""
+    reassoc, qv = C <= 4, C <= 4 and d % 4 == 0 and d <= 2048
+    stream = reassoc and not dropped and ops.dsmil_stream_ok(B, N, d, C)
+    assert qv or not stream                  # (the stream plan's d, a multiple of 8 up to 1024, is within dsmil_qv's)
+    return DSMILRoute(reassoc, qv, stream)
+
+
 class EncoderSession:
     """ONE aggregator backward for the T patch steps of a sequential training step (train_MuRCL.py:233-304 at train_stage 3).
 
@@ -890,12 +900,19 @@ class DSMILFn(torch.autograd.Function):
     """MILNet.forward for a batch of equal-length bags (models/dsmil.py:9-16,64-81,104-113).
 
     The value projection is applied AFTER pooling: bag = (A^T X) Wv^T + bv, identical to A^T (X Wv^T + bv) because every column
-    of the soft-max sums to one (dropout_v = 0).  The query projection is reassociated the same way (round 3): the attention
-    logits Q[n] . q_c / sqrt(128) with Q = X Wq^T + bq equal X[n] . v_c + const for v_c = Wq^T q_c / sqrt(128), and the soft-max
-    over n ignores the constant - so K6 is four streaming passes over X (instance scores; attention logits; pooling; and, going
-    back, dA = X dZ^T with dWc, then R = dS^T X) and a handful of [B*C]-row GEMMs; the [B*N, 128] queries and the two GEMMs over
-    all patches (forward and dWq) are never formed.  ``_DSMIL_REASSOC = False`` keeps the literal order of the reference (queries
-    by one GEMM, 3-term bf16 split for f32).  Returns (classes [B,N,C], bag [B,C,d]).
+    of the soft-max sums to one.  The query projection is reassociated the same way (round 3): the attention logits
+    Q[n] . q_c / sqrt(128) with Q = X Wq^T + bq equal X[n] . v_c + const for v_c = Wq^T q_c / sqrt(128), and the soft-max over n
+    ignores the constant - the [B*N, 128] queries and the two GEMMs over all patches (forward and dWq) are never formed.
+
+    ``dsmil_route`` picks the chain once, in ``forward``; ``backward`` reads the stored route:
+      stream   (no dropout_v, and ``ops.dsmil_stream_ok`` covers the shape - among its terms C <= 2, d <= 1024): instance scores, attention + pooling
+               (``ops.dsmil_attn_pool``) and their whole backward with dWc (``ops.dsmil_attn_pool_bwd``) are one pass over X each, around
+               three launches of [B*C]-row algebra (``ops.dsmil_qv``, ``ops.dsmil_qv_bwd``);
+      explicit (any other C <= 4): the same algebra as separate passes (rows_dot, soft-max, weighted_rowsum and their backward);
+               ``route.qv`` (d % 4 == 0, d <= 2048) keeps ``ops.dsmil_qv`` in front of them;
+      literal  (C > 4): the reference's order - queries by one GEMM over all patches, a 3-term bf16 split in f32; the row kernels
+               keep four classes in registers, so ops.py launches them once per group of four classes.
+    Returns (classes [B,N,C], bag [B,C,d], m [B,C], cmax [B,C]).
     """
     QD = 128
 
@@ -910,10 +927,10 @@ class DSMILFn(torch.autograd.Function):
         differentiable output - the arg-max launch has them in hand, and their gradient reaches the instance classifier through the
         B*C critical rows only (no dense [B,N,C] gradient, no ATen max / scatter / fill launches)."""
         B, N, d = x.shape
-        T = x.dtype
-        C = wc.shape[0]
-        QD = DSMILFn.QD
-        LD = QD + ((C + 7) // 8) * 8
+        T, C, QD = x.dtype, wc.shape[0], DSMILFn.QD
+        assert wq.shape[0] == QD
+        route = dsmil_route(B, N, d, C, keep_v is not None)
+        scale = 1.0 / math.sqrt(QD)
         x2 = x.reshape(B * N, d)
         xv = x                                                                          # the value branch's input (dsmil.py:66)
         if keep_v is not None:
@@ -922,119 +939,100 @@ class DSMILFn(torch.autograd.Function):
             xv = ops.mul(x, km, out=torch.empty_like(x))
         cls = ops.rows_dot(x2.view(1, B * N, d), wc.view(1, C, d), bias=bc).view(B * N, C)    # instance scores (dsmil.py:9-16)
         m, cmax = ops.dsmil_argmax(cls, B, N, C, want_max=True)                         # critical instances (:71-73) and their scores
-        reassoc = _DSMIL_REASSOC and C <= 4
-        qv = reassoc and _DSMIL_QV and wq.shape[0] == QD and d % 4 == 0 and d <= 2048
-        xm = None
-        if qv:
+        # front: the critical instances' queries q_c and - reassociated - v_c = Wq^T q_c; literal: the queries Q of all patches
+        xm = Q = None
+        if route.qv:
             xm, qmax, v = ops.dsmil_qv(x2, m, wq, bq, B, N, C)                          # x_m, q_c = Wq x_m + bq, Wq^T q_c: one launch
-        elif reassoc:
-            xm = ops.cast(ops.gather_rows(x2, m, B, C, N, 0, d), torch.float32)         # [B*C, d]
-            qmax = ops.gemm_nt(xm, wq, epi=ops.EPI_BIAS, bias=bq)                       # q_c = Wq x_m + bq     [B*C, 128]
+        elif route.reassoc:
+            x_m = ops.cast(ops.gather_rows(x2, m, B, C, N, 0, d), torch.float32)        # [B*C, d]
+            qmax = ops.gemm_nt(x_m, wq, epi=ops.EPI_BIAS, bias=bq)                      # q_c = Wq x_m + bq     [B*C, 128]
             v = ops.gemm_nt(qmax, ops.transposed(wq))                                   # Wq^T q_c              [B*C, d]
-        if reassoc:
-            Y = v
-            # attention + pooling from one pass over X: A = soft-max_n(X v_c / sqrt(128)) (:76-77), Z = A^T X (:78)
-            one = ops.dsmil_attn_pool(x, v.view(B, C, d), 1.0 / math.sqrt(QD)) if (_DSMIL_ONEPASS and keep_v is None) else None
-            if one is None:
-                v *= 1.0 / math.sqrt(QD)
-                A = ops.dsmil_softmax_(ops.rows_dot(x, v.view(B, C, d)))
         else:
-            # queries: one 128-column GEMM; f32: as a 3-term bf16 split on the bf16 matrix pipe (ops.gemm_nt x3)
-            Y = ops.gemm_nt(x2, wq if T == torch.float32 else ops.cast(wq, T), epi=ops.EPI_BIAS, bias=bq,
-                            out_dtype=torch.float32, x3=_DSMIL_X3)                      # Q [B*N, 128]
-            qmax = ops.gather_rows(Y, m, B, C, N, 0, QD)
-            A = ops.dsmil_attn(Y, 0, qmax, B, N, C)
-            one = None
-        A, Z = one if one is not None else (A, ops.weighted_rowsum(xv, A))              # Z = A^T X  (:78; X * keep with dropout_v)
-        bag = ops.gemm_nt(Z.view(B * C, d), wv, epi=ops.EPI_BIAS, bias=bv).view(B, C, d)
-        classes = cls.view(B, N, C)
-        ctx.save_for_backward(x, Y, m, qmax, A, Z, wv, wq, xm if qv else _placeholder(x), xv if keep_v is not None else _placeholder(x))
-        ctx.meta = (B, N, d, C, LD, reassoc, qv, keep_v is not None)
+            # one 128-column GEMM [B*N, 128]; f32: as a 3-term bf16 split on the bf16 matrix pipe (ops.gemm_nt x3)
+            Q = ops.gemm_nt(x2, wq if T == torch.float32 else ops.cast(wq, T), epi=ops.EPI_BIAS, bias=bq, out_dtype=torch.float32, x3=True)
+            qmax = ops.gather_rows(Q, m, B, C, N, 0, QD)
+        # middle: A = soft-max_n(X v_c / sqrt(128)) (:76-77) and Z = A^T X (:78; X * keep with dropout_v)
+        if route.stream:
+            one = ops.dsmil_attn_pool(x, v.view(B, C, d), scale)                        # both from one pass over X
+            assert one is not None
+            A, Z = one
+        else:
+            A = ops.dsmil_softmax_(ops.rows_dot(x, v.mul_(scale).view(B, C, d))) if route.reassoc else ops.dsmil_attn(Q, 0, qmax, B, N, C)
+            Z = ops.weighted_rowsum(xv, A)
+        bag = ops.gemm_nt(Z.view(B * C, d), wv, epi=ops.EPI_BIAS, bias=bv).view(B, C, d)    # tail: the value projection of the pooled rows
+        none = _placeholder(x)
+        ctx.save_for_backward(x, m, qmax, A, Z, wv, wq, Q if Q is not None else none, xm if xm is not None else none,
+                              xv if keep_v is not None else none)
+        ctx.meta = (B, N, d, C, route, keep_v is not None)
         ctx.params = (wc, bc, wq, bq, wv, bv)             # (the parameters themselves: the backward pass adds into their gradient buffers)
         ctx.mark_non_differentiable(m)
         ctx.set_materialize_grads(False)
         if not want_max:
             ctx.mark_non_differentiable(cmax)
-        return classes, bag, m, cmax
+        return cls.view(B, N, C), bag, m, cmax
 
     @staticmethod
     def backward(ctx, dclasses, dbag, _dm, dcmax=None):
         _enter(ctx)
-        x, Y, m, qmax, A, Z, wv, wq, xm_saved, xv = ctx.saved_tensors
-        B, N, d, C, LD, reassoc, qv, dropped = ctx.meta
-        if not dropped:
-            xv = x                                                                          # the pooled operand (X * keep under dropout_v)
-        T, QD = x.dtype, DSMILFn.QD
-        dev = x.device
+        x, m, qmax, A, Z, wv, wq, Q, xm, xv = ctx.saved_tensors
+        B, N, d, C, route, dropped = ctx.meta
+        xv = xv if dropped else x                                                           # the pooled operand (X * keep under dropout_v)
+        T, QD, dev = x.dtype, DSMILFn.QD, x.device
+        scale = 1.0 / math.sqrt(QD)
         x2 = x.reshape(B * N, d)
         dbag2 = (dbag if dbag is not None else torch.zeros((B, C, d), device=dev)).reshape(B * C, d).contiguous()
-        dwv, dbv = ops.gemm_tn_with_colsum(dbag2, Z.view(B * C, d))           # (dWv, dbv) of the value projection: one launch
+        dwv, dbv = ops.gemm_tn_with_colsum(dbag2, Z.view(B * C, d))                         # value side: (dWv, dbv) in one launch, and dZ
         dZ = ops.gemm_nt(dbag2, ops.transposed(wv)).view(B, C, d)
-        xm = None if qv else ops.gather_rows(x2, m, B, C, N, 0, d)                          # critical instances
+        if not route.qv:
+            xm = ops.gather_rows(x2, m, B, C, N, 0, d)                                      # critical instances (dsmil_qv saved its own, in f32)
         dcls = dclasses.reshape(B, N, C).float().contiguous() if dclasses is not None else None
-        # reassociated: ONE pass over X gives R (below) and dWc - neither dA nor dS is stored
-        one = ops.dsmil_attn_pool_bwd(x, dZ, A, Z, dcls, 1.0 / math.sqrt(QD)) if (reassoc and _DSMIL_ONEPASS and not dropped) else None
-        # otherwise dA = X dZ^T and, when the instance scores carry a gradient, dWc = dcls^T X from the SAME pass over X
-        fused = None
-        if one is None:
-            if dclasses is not None and not dropped:
-                fused = ops.rows_dot_wsum(x, dZ, dcls)
-            dA = fused[0] if fused is not None else ops.rows_dot(xv, dZ)                      # dA = (X * keep) dZ^T
-        dwc = dbc = None
-        cmax_done = False
-        if one is not None and qv and dcmax is not None:
-            # ... and the max-instance term's share of the instance classifier's gradient from the same second launch
-            if dclasses is not None:
-                dwc, dbc = one[1], dcls.view(B * N, C).sum(0)
-            else:
-                dwc, dbc = torch.empty((C, d), dtype=torch.float32, device=dev), torch.empty((C,), dtype=torch.float32, device=dev)
-            dwq, dbq = ops.dsmil_qv_bwd(one[0].view(B * C, d), qmax, xm_saved, wq, dcmax=dcmax.float(), dwc=dwc, dbc=dbc,
-                                        accumulate=dclasses is not None)
-            cmax_done = True
-        elif one is not None and qv:
-            dwq, dbq = ops.dsmil_qv_bwd(one[0].view(B * C, d), qmax, xm_saved, wq)         # dq = R Wq^T, dWq = q^T R + dq^T x_m, dbq
-        elif one is not None:
-            R = one[0].view(B * C, d)
-            dqmax = ops.gemm_nt(R, wq)                                                      # [B*C, 128]
-            dwq = ops.gemm_tn(qmax, R)                                                      # [128, d]
-            dbq = None
-        elif reassoc:
-            # dS weights the rows of X once more: R_c = sum_n dS[n,c] X[n] / sqrt(128) is the gradient of v_c, and
-            #   sum_n dQ[n]^T X[n] = qmax^T R,   dqmax = sum_n dS[n,c] Q[n] / sqrt(128) = R Wq^T  (+ bq sum_n dS[n,c], and a soft-max
-            #   gradient sums to nothing)
-            R = ops.weighted_rowsum(x, ops.dsmil_softmax_bwd(A, dA)).view(B * C, d)
-            R *= 1.0 / math.sqrt(QD)
-            dqmax = ops.gemm_nt(R, wq)                                                      # [B*C, 128]
-            dwq = ops.gemm_tn(qmax, R)                                                      # [128, d]
-            dbq = None
+        # attention and pooling -> R = dL/dv_c (literal: dQ, dqmax), and the dense dWc = dcls^T X where the pass over X gives it on the way
+        if route.stream:
+            one = ops.dsmil_attn_pool_bwd(x, dZ, A, Z, dcls, scale)                         # ONE pass over X: neither dA nor dS is stored
+            assert one is not None
+            R, dwc = one[0].view(B * C, d), one[1]
         else:
-            dQ = torch.empty((B * N, QD), dtype=torch.float32, device=dev)                  # written in full below
-            dqmax = ops.dsmil_attn_bwd(A, dA, Y, 0, qmax, dQ, B, N, C)
-            dwq = ops.gemm_tn(dQ if T == torch.float32 else ops.cast(dQ, T), x2, x3=_DSMIL_X3)  # [128, d]: one tile row
-            dbq = ops.colsum(dQ)
-        if one is not None and qv:
-            pass
-        elif reassoc:
-            ops.gemm_tn(dqmax, xm_saved if qv else ops.cast(xm, torch.float32), out=dwq)
-            dbq = ops.colsum(dqmax) if dbq is None else ops.colsum(dqmax, out=dbq, accumulate=True)
-        else:
-            ops.gemm_tn(dqmax if T == torch.float32 else ops.cast(dqmax, T), xm, out=dwq)
-            dbq = ops.colsum(dqmax) if dbq is None else ops.colsum(dqmax, out=dbq, accumulate=True)
-        if dclasses is not None and not cmax_done:
-            # the C instance-score columns: dWc = dcls^T X as a weighted row sum over all patches (a 128-wide wgrad tile
-            # for 2 columns would read X a second time through the GEMM path)
-            if one is not None:
-                dwc = one[1]
+            # dA = (X * keep) dZ^T and, when the instance scores carry a gradient, dWc from the SAME pass over X
+            fused = ops.rows_dot_wsum(x, dZ, dcls) if (dcls is not None and not dropped) else None
+            dA, dwc = fused if fused is not None else (ops.rows_dot(xv, dZ), None)
+            if route.reassoc:
+                R = ops.weighted_rowsum(x, ops.dsmil_softmax_bwd(A, dA)).view(B * C, d)     # dS weights the rows of X once more:
+                R *= scale                                                                  # R_c = sum_n dS[n,c] X[n] / sqrt(128)
             else:
-                dwc = fused[1] if fused is not None else ops.weighted_rowsum(x2.view(1, B * N, d), dcls.view(1, B * N, C)).view(C, d)
-            dbc = dcls.view(B * N, C).sum(0)
-        if dcmax is not None and not cmax_done:
-            # paths without the two-launch [B*C]-row algebra: the same sums in plain tensor ops on the B*C critical rows
-            xm_f = (xm_saved if qv else ops.cast(ops.gather_rows(x2, m, B, C, N, 0, d), torch.float32)).view(B, C, d)
-            g = dcmax.float().view(B, C, 1)
-            dwc_m, dbc_m = (g * xm_f).sum(0), g.view(B, C).sum(0)
-            dwc = dwc_m if dwc is None else dwc + dwc_m
-            dbc = dbc_m if dbc is None else dbc + dbc_m
+                dQ = torch.empty((B * N, QD), dtype=torch.float32, device=dev)              # written in full below
+                dqmax = ops.dsmil_attn_bwd(A, dA, Q, 0, qmax, dQ, B, N, C)
+        if route.stream and dcmax is not None:
+            # query side and instance classifier in one: dsmil_qv_bwd's second launch adds the max-instance term of (dWc, dbc) to the dense one
+            dwc, dbc = (dwc, dcls.view(B * N, C).sum(0)) if dcls is not None else \
+                (torch.empty((C, d), dtype=torch.float32, device=dev), torch.empty((C,), dtype=torch.float32, device=dev))
+            dwq, dbq = ops.dsmil_qv_bwd(R, qmax, xm, wq, dcmax=dcmax.float(), dwc=dwc, dbc=dbc, accumulate=dcls is not None)
+        else:
+            if route.stream:                                                                # query side
+                dwq, dbq = ops.dsmil_qv_bwd(R, qmax, xm, wq)                                # dq = R Wq^T, dWq = q^T R + dq^T x_m, dbq
+            elif route.reassoc:
+                # sum_n dQ[n]^T X[n] = qmax^T R,  dqmax = sum_n dS[n,c] Q[n] / sqrt(128) = R Wq^T (+ bq sum_n dS[n,c]: a soft-max gradient sums to 0)
+                dqmax = ops.gemm_nt(R, wq)                                                  # [B*C, 128]
+                dwq = ops.gemm_tn(qmax, R)                                                  # [128, d]
+                ops.gemm_tn(dqmax, xm if route.qv else ops.cast(xm, torch.float32), out=dwq)
+                dbq = ops.colsum(dqmax)
+            else:
+                dwq = ops.gemm_tn(dQ if T == torch.float32 else ops.cast(dQ, T), x2, x3=True)   # [128, d]: one tile row
+                dbq = ops.colsum(dQ)
+                ops.gemm_tn(dqmax if T == torch.float32 else ops.cast(dqmax, T), xm, out=dwq)
+                ops.colsum(dqmax, out=dbq, accumulate=True)
+            # instance classifier, dense term: where no pass over X gave dWc above, a weighted row sum over all patches (not a 128-wide wgrad tile) ...
+            dbc = None
+            if dcls is not None:
+                if dwc is None:
+                    dwc = ops.weighted_rowsum(x2.view(1, B * N, d), dcls.view(1, B * N, C)).view(C, d)
+                dbc = dcls.view(B * N, C).sum(0)
+            if dcmax is not None:
+                # ... and the max-instance term: the same sums as dsmil_qv_bwd's, in plain tensor ops on the B*C critical rows
+                xm_f = (xm if route.qv else ops.cast(ops.gather_rows(x2, m, B, C, N, 0, d), torch.float32)).view(B, C, d)
+                g = dcmax.float().view(B, C, 1)
+                dwc_m, dbc_m = (g * xm_f).sum(0), g.view(B, C).sum(0)
+                dwc = dwc_m if dwc is None else dwc + dwc_m
+                dbc = dbc_m if dbc is None else dbc + dbc_m
         # six parameter gradients: ONE launch adds them to the optimizer's pre-seated buffers (no AccumulateGrad add per parameter)
         dwc, dbc, dwq, dbq, dwv, dbv = _pgrads(*zip((dwc, dbc, dwq, dbq, dwv, dbv), ctx.params))
         return None, dwc, dbc, dwq, dbq, dwv, dbv, None, None

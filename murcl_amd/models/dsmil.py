@@ -24,7 +24,7 @@ class BClassifier(nn.Module):
         if not 0.0 <= dropout_v < 1.0:
             raise ValueError(f"dropout probability has to be in [0, 1), got {dropout_v}")
         # dropout_v > 0 (no reference script sets it, dsmil.py:118): Dropout on the value branch's input while training - built for
-        # the constructor's contract (round 6), on the explicit chain of DSMILFn instead of its one-pass kernels
+        # the constructor's contract (round 6), on DSMILFn's explicit route (functional.dsmil_route) instead of its one-pass kernels
         self.dropout_v = float(dropout_v)
         self.q = nn.Linear(input_size, 128)
         self.v = nn.Sequential(nn.Dropout(dropout_v), nn.Linear(input_size, input_size))

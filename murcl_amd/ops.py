@@ -1063,7 +1063,16 @@ def gather_rows(src, m, B, C, N, col0, width):
     return out
 
 
+def _class_groups(C):
+    """The row kernels of dsmil.hip keep at most four classes in registers: more classes (DSMIL's literal route) run as launches of
+    four, the pieces joined by torch."""
+    return [(c, min(c + 4, C)) for c in range(0, C, 4)]
+
+
 def dsmil_attn(Y, qcol0, qmax, B, N, C):
+    if C > 4:
+        q = qmax.view(B, C, -1)
+        return torch.cat([dsmil_attn(Y, qcol0, q[:, a:b].reshape(B * (b - a), -1).contiguous(), B, N, b - a) for a, b in _class_groups(C)], 2)
     A = torch.empty((B, N, C), dtype=torch.float32, device=Y.device)
     check(_lib.lib().murcl_dsmil_attn(ptr(Y), Y.stride(0), qcol0, ptr(qmax), B, N, C, ptr(A), stream()), "dsmil_attn")
     return A
@@ -1107,6 +1116,11 @@ def dsmil_qv_bwd(R, qmax, xm, wq, dcmax=None, dwc=None, dbc=None, accumulate=Tru
     check(_lib.lib().murcl_dsmil_qv_bwd_cls(ptr(R), ptr(qmax), ptr(xm), ptr(wq), BC, d, ptr(dq), ptr(dwq), ptr(dbq), ptr(dcmax), C,
                                             ptr(dwc), ptr(dbc), int(accumulate), stream()), "dsmil_qv_bwd_cls")
     return dwq, dbq
+
+
+def dsmil_stream_ok(B, N, d, C):
+    """Do the one-pass kernels (dsmil_attn_pool, dsmil_attn_pool_bwd) cover this shape?"""
+    return bool(_lib.lib().murcl_dsmil_stream_plan(B, N, d, C))
 
 
 def dsmil_attn_pool(X, v, scale=1.0):
@@ -1161,9 +1175,11 @@ def dsmil_softmax_bwd(A, dA):
 def weighted_rowsum(X, A, into=None):
     """Z[b,c,:] = sum_n A[b,n,c] X[b,n,:]   X [B,N,d] (f32/bf16), A [B,N,C] f32 -> Z [B,C,d] f32.  ``into``: a [B,C,d] f32 tensor the
     sums are ADDED to (cleared by the caller: ``murcl_weighted_rowsum_acc``, no fill launch)."""
-    X, A = _c(X), _c(A)
     B, N, d = X.shape
     C = A.shape[2]
+    if C > 4 and into is None:
+        return torch.cat([weighted_rowsum(X, A[:, :, a:b]) for a, b in _class_groups(C)], 1)
+    X, A = _c(X), _c(A)
     if into is not None:
         assert into.is_contiguous() and into.dtype == torch.float32 and into.numel() == B * C * d
         with _span(lambda: (f"weighted_rowsum<{_DT_NAME[X.dtype]}>", dict(bytes=X.numel() * X.element_size(), flops=2.0 * B * N * d * C))):
@@ -1183,9 +1199,11 @@ def weighted_rowsum(X, A, into=None):
 
 def rows_dot(X, V, bias=None):
     """out[b,n,c] = X[b,n,:] . V[b,c,:] (+ bias[c])."""
-    X, V = _c(X), _c(V)
     B, N, d = X.shape
     C = V.shape[1]
+    if C > 4:
+        return torch.cat([rows_dot(X, V[:, a:b], None if bias is None else bias[a:b]) for a, b in _class_groups(C)], 2)
+    X, V = _c(X), _c(V)
     out = torch.empty((B, N, C), dtype=torch.float32, device=X.device)
     if bias is not None:
         bias = _c(bias)
@@ -1213,6 +1231,15 @@ def rows_dot_wsum(X, V, G):
 
 
 def dsmil_attn_bwd(A, dA, Y, qcol0, qmax, dY, B, N, C):
+    if C > 4:                                             # dY sums over the classes: the first group writes it, the others are added
+        q, parts = qmax.view(B, C, -1), []
+        for a, b in _class_groups(C):
+            dYg = dY if a == 0 else torch.empty_like(dY)
+            parts.append(dsmil_attn_bwd(A[:, :, a:b].contiguous(), dA[:, :, a:b], Y, qcol0, q[:, a:b].reshape(B * (b - a), -1).contiguous(), dYg,
+                                        B, N, b - a).view(B, b - a, -1))
+            if a:
+                dY += dYg
+        return torch.cat(parts, 1).view(B * C, -1)
     dqmax = torch.empty((B * C, qmax.shape[1]), dtype=torch.float32, device=Y.device)
     dots = torch.empty((B * C,), dtype=torch.float32, device=Y.device)
     check(_lib.lib().murcl_dsmil_attn_bwd(ptr(A), ptr(_c(dA)), ptr(Y), Y.stride(0), qcol0, ptr(qmax), B, N, C, ptr(dY),

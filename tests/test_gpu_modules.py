@@ -547,8 +547,9 @@ def test_dsmil_vs_reference_golden(golden):
     np.testing.assert_allclose(b1.detach().cpu().numpy(), g["bag_single"], rtol=1e-4, atol=1e-5)
 
 
-@pytest.mark.parametrize("B,N,d,C", [(2, 1000, 1024, 2), (4, 333, 512, 3)])
+@pytest.mark.parametrize("B,N,d,C", [(2, 1000, 1024, 2), (4, 333, 512, 3), (2, 2050, 64, 5)])
 def test_dsmil_vs_oracle_full_grads(B, N, d, C):
+    """(2, 2050, 64, 5) reaches the literal route (C > 4) by shape: 4100 ragged rows, past both thresholds of the 3-term split."""
     m = _dsmil(6, d, C)
     p = {k: v.clone().requires_grad_() for k, v in P.to_torch(P.dsmil(6, d, C)).items()}
     x = T(P.bags(6, f"x{B}{N}", B, N, d))
@@ -811,9 +812,9 @@ def test_dsmil_reassociated_attention_equals_the_literal_order(monkeypatch, dtyp
         return classes.detach(), bag.detach(), {k: v.grad.clone() for k, v in m.named_parameters() if v.grad is not None}
 
     outs = {}
-    for name, re, one in (("onepass", True, True), ("reassoc", True, False), ("literal", False, False)):
-        monkeypatch.setattr(functional, "_DSMIL_REASSOC", re)
-        monkeypatch.setattr(functional, "_DSMIL_ONEPASS", one)
+    assert functional.dsmil_route(B, N, d, 2, False) == (True, True, True)    # what the shape takes by itself: the one-pass kernels
+    for name, route in (("onepass", (True, True, True)), ("reassoc", (True, True, False)), ("literal", (False, False, False))):
+        monkeypatch.setattr(functional, "dsmil_route", lambda *a, route=route: functional.DSMILRoute(*route))
         outs[name] = run()
     tol = 1e-4 if dtype == torch.float32 else 2e-2
     lit = outs["literal"]
@@ -829,7 +830,7 @@ def test_dsmil_reassociated_attention_equals_the_literal_order(monkeypatch, dtyp
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("also_dense", [False, True])
-def test_dsmil_max_instance_scores_come_out_of_the_argmax_launch(dtype, also_dense, monkeypatch):
+def test_dsmil_max_instance_scores_come_out_of_the_argmax_launch(dtype, also_dense):
     """Round 4: ``_run(want_max=True)`` returns the max-instance class scores (train_RLMIL.py:516, ``torch.max(outputs_ins, 0)``) as its
     own differentiable output: equal to ``classes.max(1)[0]`` bit for bit, and a loss on it gives the parameter gradients of the dense
     route (ATen max -> scatter into a [B,N,C] gradient -> the streaming backward with dcls) - alone and together with a dense term."""
