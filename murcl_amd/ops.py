@@ -1233,12 +1233,13 @@ def rows_dot_wsum(X, V, G):
 def dsmil_attn_bwd(A, dA, Y, qcol0, qmax, dY, B, N, C):
     if C > 4:                                             # dY sums over the classes: the first group writes it, the others are added
         q, parts = qmax.view(B, C, -1), []
+        cols = slice(qcol0, qcol0 + q.shape[2])           # all a launch writes of a dY row: the rest of a scratch row is not data
         for a, b in _class_groups(C):
             dYg = dY if a == 0 else torch.empty_like(dY)
             parts.append(dsmil_attn_bwd(A[:, :, a:b].contiguous(), dA[:, :, a:b], Y, qcol0, q[:, a:b].reshape(B * (b - a), -1).contiguous(), dYg,
                                         B, N, b - a).view(B, b - a, -1))
             if a:
-                dY += dYg
+                dY[:, cols] += dYg[:, cols]
         return torch.cat(parts, 1).view(B * C, -1)
     dqmax = torch.empty((B * C, qmax.shape[1]), dtype=torch.float32, device=Y.device)
     dots = torch.empty((B * C,), dtype=torch.float32, device=Y.device)

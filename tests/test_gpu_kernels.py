@@ -1,4 +1,6 @@
-"""Kernel-level parity on a real MI355X: every C-ABI entry point against CPU math / the oracle.
+"""Kernel-level parity on a real MI355X: the GEMM, pooling, loss, optimizer and element-wise entry points of the C-ABI against CPU
+math / the oracle.  The rest: test_gpu_row_kernels.py (DSMIL row kernels, CLAM instance branch), test_gpu_ppo_kernels.py (the
+sampler's heads and launch sequences), test_gpu_kmeans.py and test_gpu_subbag.py (clustering, sub-bag selection).
 
 fp32 kernels (exact-f32 MFMA) are held to 1e-4 relative (BASELINE.json north_star); bf16 kernels
 are compared with the same math evaluated on the bf16-rounded inputs (tolerance stated per test).
