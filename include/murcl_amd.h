@@ -139,6 +139,31 @@ int murcl_panel_gemm_drop(const void* A, const void* W, void* C, int M, int N, i
 int murcl_cu_budget(void);
 int murcl_set_cu_budget(int cus);
 
+/* Deterministic mode (csrc/runtime.hip): process-wide host state, off by default; murcl_set_deterministic returns the previous
+ * state.  Launchers and planners read it when they launch, so a captured graph keeps whichever form was captured.  While it is on,
+ * no launcher picks a form in which several workgroups add floats into one address in arrival order: same device, same build, same
+ * shapes, same CU budget, same inputs -> the same bits.  What changes:
+ *   murcl_gemm_tn_plan / _grouped  no product plans as WIDE or ATOMIC: those run as PARTS (any row count, every split has rows); the
+ *                                  column-sum launches in front of a product take murcl_colsum_det's form, and the workspace bytes
+ *                                  the plan reports cover both;
+ *   murcl_gemm_nt                  the bag-level f32 form keeps its reduction unsplit (no K split into a zeroed C);
+ *   murcl_colsum, murcl_weighted_rowsum, murcl_weighted_rowsum_acc   own no workspace: ONE row split (a single writer or adder per
+ *                                  address; slow on long inputs - call the _det entries below).  The library's own calls of
+ *                                  murcl_colsum stay off that slow form: murcl_panel_gemm adds up its per-workgroup partial rows
+ *                                  (at most 256, one per CU: a single split in either mode), and murcl_ppo_epoch / the column sums
+ *                                  in front of a murcl_gemm_tn_grouped product go through murcl_colsum_det in the mode;
+ *   murcl_ppo_epoch[_wt]           murcl_ppo_epoch_workspace grows by what its weight gradients (PARTS beyond 512 rollout rows)
+ *                                  and the column sums of dgh need; query it in the mode the epoch will run in;
+ *   murcl_dsmil_attn_bwd           refuses bags of more than one 64-row block (-1): call murcl_dsmil_attn_bwd_det.
+ * The _det entries (declared beside what they restate) run in either mode: splits as in the default form, every split STORES its
+ * partial result to a caller-owned workspace (the *_workspace query gives the bytes, 0 = one split; 16-byte aligned), and one reduce
+ * launch adds the splits in an order fixed by the split count.
+ * murcl_float_atomic_launches: how many launches so far took a form whose float result depends on arrival order (every launcher
+ * counts its own) - it moves in default mode on the shapes that reach such a form and stays put in deterministic mode. */
+int murcl_set_deterministic(int on);
+int murcl_deterministic(void);
+long murcl_float_atomic_launches(void);
+
 /* Box calibration for bench.py (csrc/runtime.hip; not on the product path, no reference counterpart): a streaming copy of `bytes`
  * (multiple of 16) with 16-byte accesses, and a register-only loop of 256 CUs x 8 waves x iters x 4 v_mfma_f32_16x16x32_bf16 (16384 FLOP
  * each) writing 256*512 floats - timed by the caller, they say what HBM rate and matrix clock THIS box sustains. */
@@ -288,6 +313,11 @@ int murcl_weighted_rowsum(const void* X, const float* A, float* Z, int B, int N,
 /* The same ADDED into Z (no zero fill in front: the caller cleared Z, e.g. through murcl_softmax_rows_parts). */
 int murcl_weighted_rowsum_acc(const void* X, const float* A, float* Z, int B, int N, int d, int C, int dtype,
                               murcl_stream_t stream);
+/* Fixed-order form of the two above (accumulate == 0: murcl_weighted_rowsum, Z written; != 0: murcl_weighted_rowsum_acc, added into
+ * Z): ws [splits][B][C][d] f32 of murcl_weighted_rowsum_workspace bytes. */
+long murcl_weighted_rowsum_workspace(int B, int N, int d, int C);
+int murcl_weighted_rowsum_det(const void* X, const float* A, float* Z, int B, int N, int d, int C, int dtype, int accumulate,
+                              float* ws, long ws_bytes, murcl_stream_t stream);
 int murcl_rows_dot(const void* X, const float* V, float* out, int B, int N, int d, int C, int dtype,
                    murcl_stream_t stream);
 /* the same + bias[c] (may be NULL): the instance classifier's Linear(d, C) (dsmil.py:9,15) in one launch */
@@ -302,6 +332,12 @@ int murcl_rows_dot_wsum(const void* X, const float* V, const float* G, float* ou
                         int dtype, murcl_stream_t stream);
 int murcl_dsmil_attn_bwd(const float* A, const float* dA, const float* Q, int ldq, int qcol0, const float* qmax, int B,
                          int N, int C, float* dY, int ldy, float* dqmax, float* dots_ws /* [B*C] */, murcl_stream_t stream);
+/* Fixed-order form of murcl_dsmil_attn_bwd: ws [row blocks][B][C][128] f32 of murcl_dsmil_attn_bwd_workspace bytes; dqmax 16-byte
+ * aligned. */
+long murcl_dsmil_attn_bwd_workspace(int B, int N, int C);
+int murcl_dsmil_attn_bwd_det(const float* A, const float* dA, const float* Q, int ldq, int qcol0, const float* qmax, int B,
+                             int N, int C, float* dY, int ldy, float* dqmax, float* dots_ws /* [B*C] */, float* ws, long ws_bytes,
+                             murcl_stream_t stream);
 
 /* K4/K5 -- CLAM-SB pieces (models/clam.py); the fc and gate projections are murcl_gemm_nt / murcl_panel_gemm calls.
  * gated_score: s[n] = sum_d tanh(U[n,d])*sigmoid(U[n,D+d])*wc[d] + bc (clam.py:56-59), optional dropout keep
@@ -389,6 +425,11 @@ int murcl_ppo_loss(const float* logp, const float* old_logp, const float* value,
 int murcl_cast(const void* x, void* y, long n, int dtype_in, int dtype_out, murcl_stream_t stream);
 int murcl_transpose_cast(const float* x, void* y, int R, int C, int dtype_out, murcl_stream_t stream);
 int murcl_colsum(const void* x, float* out, int R, int N, int ld, int dtype, int accumulate, murcl_stream_t stream);
+/* Fixed-order form of murcl_colsum (R > 512 rows: up to 64 row splits): ws [splits][N rounded up to 4] f32 of
+ * murcl_colsum_workspace bytes. */
+long murcl_colsum_workspace(int R, int N, int dtype);
+int murcl_colsum_det(const void* x, float* out, int R, int N, int ld, int dtype, int accumulate, float* ws, long ws_bytes,
+                     murcl_stream_t stream);
 int murcl_relu_bwd(const float* dy, const float* y, float* dx, long n, murcl_stream_t stream);
 
 /* K7/K10 -- one nn.GRU time step's gate math (rlmil.py:47,78,199,213-217); the two projections are

@@ -27,6 +27,9 @@ SIGNATURES = {
     "murcl_panel_gemm_drop": [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _F, ctypes.c_ulonglong, ctypes.c_ulonglong, _P],
     "murcl_cu_budget": [],
     "murcl_set_cu_budget": [_I],
+    "murcl_set_deterministic": [_I],
+    "murcl_deterministic": [],
+    "murcl_float_atomic_launches": [],
     "murcl_calib_copy": [_P, _P, _L, _P],
     "murcl_calib_mfma_bf16": [_P, _I, _P],
     "murcl_abmil_pool_workspace": [_I, _I, _I, _c.POINTER(_I), _c.POINTER(_I)],
@@ -52,11 +55,15 @@ SIGNATURES = {
     "murcl_dsmil_attn": [_P, _I, _I, _P, _I, _I, _I, _P, _P],
     "murcl_weighted_rowsum": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "murcl_weighted_rowsum_acc": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "murcl_weighted_rowsum_workspace": [_I, _I, _I, _I],
+    "murcl_weighted_rowsum_det": [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P],
     "murcl_rows_dot": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
     "murcl_rows_dot_bias": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "murcl_rows_dot_wsum_plan": [_I, _I, _I, _I],
     "murcl_rows_dot_wsum": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "murcl_dsmil_attn_bwd": [_P, _P, _P, _I, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P],
+    "murcl_dsmil_attn_bwd_workspace": [_I, _I, _I],
+    "murcl_dsmil_attn_bwd_det": [_P, _P, _P, _I, _I, _P, _I, _I, _I, _P, _I, _P, _P, _P, _L, _P],
     "murcl_gated_score_fwd": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _F, ctypes.c_ulonglong, ctypes.c_ulonglong, _P],
     "murcl_gated_score_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _F, ctypes.c_ulonglong, ctypes.c_ulonglong, _P],
     "murcl_dsmil_softmax": [_P, _I, _I, _I, _P],
@@ -93,6 +100,8 @@ SIGNATURES = {
     "murcl_cast": [_P, _P, _L, _I, _I, _P],
     "murcl_transpose_cast": [_P, _P, _I, _I, _I, _P],
     "murcl_colsum": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "murcl_colsum_workspace": [_I, _I, _I],
+    "murcl_colsum_det": [_P, _P, _I, _I, _I, _I, _I, _P, _L, _P],
     "murcl_relu_bwd": [_P, _P, _P, _L, _P],
     "murcl_gru_gates_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "murcl_gru_gates_bwd_into": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
@@ -120,7 +129,8 @@ SIGNATURES = {
     "murcl_sgd_step": [_P, _P, _P, _L, _F, _F, _I, _F, _I, _I, _P],
 }
 _RESTYPE = {"murcl_ntxent_workspace_bytes": _L, "murcl_ntxent_xchg_bytes": _L, "murcl_kmeans_workspace_bytes": _L, "murcl_ppo_act_workspace": _L, "murcl_gemm_tn_plan": _L,
-            "murcl_ppo_epoch_workspace": _L}
+            "murcl_ppo_epoch_workspace": _L, "murcl_float_atomic_launches": _L, "murcl_colsum_workspace": _L,
+            "murcl_weighted_rowsum_workspace": _L, "murcl_dsmil_attn_bwd_workspace": _L}
 
 
 

@@ -20,6 +20,13 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 extern "C" int murcl_cu_budget(void);      // runtime.hip: CUs the persistent launches size their one round of workgroups for (256 by default)
 
+// Deterministic mode (runtime.hip).  A launcher calls murcl_note_float_atomic_launch() each time it launches a form in which more
+// than one workgroup adds floats into one address (murcl_float_atomic_launches counts them); murcl_parts_reduce (elementwise.hip)
+// is the fixed-order end of the `_det` forms: out[i] (+)= sum_s part[s * np + i], i < n, np = n rounded up to 4 floats.
+void murcl_note_float_atomic_launch(void);
+int murcl_parts_reduce(const float* part, float* out, long n, int nsplit, int accumulate, hipStream_t s);
+static inline long murcl_parts_pitch(long n) { return (n + 3) & ~3L; }
+
 // hipFuncSetAttribute applies to the current device only: call sites remember which devices they have prepared
 // (one process per GPU is the norm, but a process that drives several devices must raise the LDS limit on each).
 struct MurclOncePerDevice {

@@ -174,7 +174,9 @@ extern "C" int murcl_dsmil_softmax(float* S, int B, int N, int C, hipStream_t s)
 // Z[b,c,:] = sum_n A[b,n,c] X[b,n,:]      (one streaming pass over X; C <= 4)
 // grid (B, row splits).  A thread owns 8 consecutive columns (16-byte loads for bf16), G = d/8 column groups and
 // 256/G row lanes per workgroup; the row lanes meet in LDS and the workgroup adds its partial sums atomically.
-template <typename T>
+// PARTS (the fixed-order form, murcl_weighted_rowsum_det): row split y STORES its sums to Z[y][B][C][d] (16-byte stores, one
+// writer per element); murcl_parts_reduce adds the splits.
+template <typename T, bool PARTS = false>
 __global__ __launch_bounds__(256) void weighted_rowsum_kernel(const T* __restrict__ X, const float* __restrict__ A,
                                                               int N, int d, int C, int rows_per_block,
                                                               float* __restrict__ Z) {
@@ -234,31 +236,46 @@ __global__ __launch_bounds__(256) void weighted_rowsum_kernel(const T* __restric
                 for (int r = 0; r < RL; ++r)
 #pragma unroll
                     for (int e = 0; e < 8; ++e) t[e] += red[r * G + cg][e];
+                if constexpr (PARTS) {
+                    float* zp = Z + (((size_t)blockIdx.y * gridDim.x + b) * C + c) * d + c0;
+                    *(f32x4*)zp = f32x4{t[0], t[1], t[2], t[3]};
+                    *(f32x4*)(zp + 4) = f32x4{t[4], t[5], t[6], t[7]};
+                } else {
 #pragma unroll
-                for (int e = 0; e < 8; ++e) atomicAdd(Z + ((size_t)b * C + c) * d + c0 + e, t[e]);
+                    for (int e = 0; e < 8; ++e) atomicAdd(Z + ((size_t)b * C + c) * d + c0 + e, t[e]);      // deterministic mode: one split per bag = one adder
+                }
             }
         }
     }
 }
+// rows per split and row splits (every split has rows); one split: a single adder per address
+static void weighted_rowsum_plan(int B, int N, bool split, int& rpb, int& gy) {
+    int splits = split ? (WR_WGS + B - 1) / B : 1;
+    if (splits > (N + 63) / 64) splits = (N + 63) / 64;
+    if (splits < 1) splits = 1;
+    rpb = (N + splits - 1) / splits;
+    gy = N > 0 ? (N + rpb - 1) / rpb : 1;
+    if (rpb < 1) rpb = 1;
+}
+// In deterministic mode these two entry points, which own no workspace, keep ONE row split per bag (a single adder per address:
+// nothing depends on arrival order); murcl_weighted_rowsum_det below is the split form with a fixed summation order.
 static int weighted_rowsum_launch(const void* X, const float* A, float* Z, int B, int N, int d, int C, int dtype, bool zero,
                                   hipStream_t s) {
     if (B <= 0) return 0;
     if (C > 4 || d % 8) return -1;
+    if (dtype != MURCL_DTYPE_F32 && dtype != MURCL_DTYPE_BF16) return -1;
     if (zero) {
         hipError_t e = hipMemsetAsync(Z, 0, (size_t)B * C * d * 4, s);
         if (e != hipSuccess) return (int)e;
     }
-    int splits = (WR_WGS + B - 1) / B;
-    if (splits > (N + 63) / 64) splits = (N + 63) / 64;
-    if (splits < 1) splits = 1;
-    const int rpb = (N + splits - 1) / splits;
-    dim3 grid(B, (N + rpb - 1) / rpb);
+    int rpb, gy;
+    weighted_rowsum_plan(B, N, !murcl_deterministic(), rpb, gy);
+    dim3 grid(B, gy);
+    if (gy > 1) murcl_note_float_atomic_launch();           // the splits of a bag meet through float atomics
     if (dtype == MURCL_DTYPE_F32)
         hipLaunchKernelGGL(weighted_rowsum_kernel<float>, grid, dim3(256), 0, s, (const float*)X, A, N, d, C, rpb, Z);
-    else if (dtype == MURCL_DTYPE_BF16)
-        hipLaunchKernelGGL(weighted_rowsum_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)X, A, N, d, C, rpb, Z);
     else
-        return -1;
+        hipLaunchKernelGGL(weighted_rowsum_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)X, A, N, d, C, rpb, Z);
     return MURCL_CHECK_LAUNCH();
 }
 extern "C" int murcl_weighted_rowsum(const void* X, const float* A, float* Z, int B, int N, int d, int C, int dtype,
@@ -269,6 +286,45 @@ extern "C" int murcl_weighted_rowsum(const void* X, const float* A, float* Z, in
 extern "C" int murcl_weighted_rowsum_acc(const void* X, const float* A, float* Z, int B, int N, int d, int C, int dtype,
                                          hipStream_t s) {
     return weighted_rowsum_launch(X, A, Z, B, N, d, C, dtype, false, s);
+}
+// murcl_weighted_rowsum (accumulate == 0: Z written, no fill launch) and murcl_weighted_rowsum_acc (accumulate != 0: added to Z)
+// with the row splits added in a fixed order (restates the two above: same splits, same sums inside a split): the splits store
+// to ws[split][B][C][d], one reduce launch adds them.  ws: at least murcl_weighted_rowsum_workspace bytes, 16-byte aligned; 0
+// bytes = one split per bag, no workspace read.
+extern "C" long murcl_weighted_rowsum_workspace(int B, int N, int d, int C) {
+    if (B <= 0 || N <= 0 || d <= 0 || C <= 0) return 0;
+    int rpb, gy;
+    weighted_rowsum_plan(B, N, true, rpb, gy);
+    return gy > 1 ? (long)gy * B * C * d * 4 : 0;
+}
+extern "C" int murcl_weighted_rowsum_det(const void* X, const float* A, float* Z, int B, int N, int d, int C, int dtype,
+                                         int accumulate, float* ws, long ws_bytes, hipStream_t s) {
+    if (B <= 0) return 0;
+    if (C < 1 || C > 4 || d % 8 || d <= 0) return -1;
+    if (dtype != MURCL_DTYPE_F32 && dtype != MURCL_DTYPE_BF16) return -1;
+    int rpb, gy;
+    weighted_rowsum_plan(B, N, true, rpb, gy);
+    const long n = (long)B * C * d;
+    if (gy == 1) {                                          // one adder per address: the plain launch
+        if (!accumulate) {
+            hipError_t e = hipMemsetAsync(Z, 0, (size_t)n * 4, s);
+            if (e != hipSuccess) return (int)e;
+        }
+        if (dtype == MURCL_DTYPE_F32)
+            hipLaunchKernelGGL(weighted_rowsum_kernel<float>, dim3(B, 1), dim3(256), 0, s, (const float*)X, A, N, d, C, rpb, Z);
+        else
+            hipLaunchKernelGGL(weighted_rowsum_kernel<bf16_t>, dim3(B, 1), dim3(256), 0, s, (const bf16_t*)X, A, N, d, C, rpb, Z);
+        return MURCL_CHECK_LAUNCH();
+    }
+    if (!ws || ws_bytes < (long)gy * n * 4 || (uintptr_t)ws % 16) return -1;
+    dim3 grid(B, gy);
+    if (dtype == MURCL_DTYPE_F32)
+        hipLaunchKernelGGL((weighted_rowsum_kernel<float, true>), grid, dim3(256), 0, s, (const float*)X, A, N, d, C, rpb, ws);
+    else
+        hipLaunchKernelGGL((weighted_rowsum_kernel<bf16_t, true>), grid, dim3(256), 0, s, (const bf16_t*)X, A, N, d, C, rpb, ws);
+    const int rc = MURCL_CHECK_LAUNCH();
+    if (rc) return rc;
+    return murcl_parts_reduce(ws, Z, n, gy, accumulate, s);
 }
 
 // out[b,n,c] = X[b,n,:] . V[b,c,:]      (dA = X dZ^T; C <= 4).  A wave walks `RPW` rows; a lane owns 8 consecutive
@@ -502,6 +558,8 @@ __global__ __launch_bounds__(256) void dsmil_attn_dots_kernel(const float* __res
     if (tid == 0) dots[b * C + c] = red[0];
 }
 // rows spread over the chip: dY rows and this workgroup's share of dqmax (N/DS_RPB atomic adders per address)
+// PARTS (the fixed-order form, murcl_dsmil_attn_bwd_det): row block x STORES its share to dqmax[x][B][C][DS_Q] (16-byte stores)
+template <bool PARTS = false>
 __global__ __launch_bounds__(256) void dsmil_attn_bwd_kernel(const float* __restrict__ A, const float* __restrict__ dA,
                                                              const float* __restrict__ Q, int ldq, int qcol0,
                                                              const float* __restrict__ qmax, const float* __restrict__ dots_g,
@@ -544,24 +602,60 @@ __global__ __launch_bounds__(256) void dsmil_attn_bwd_kernel(const float* __rest
             f32x4 t = red[0][kl][c];
 #pragma unroll
             for (int r = 1; r < 8; ++r) t += red[r][kl][c];
+            if constexpr (PARTS) {
+                *(f32x4*)(dqmax + (((size_t)blockIdx.x * gridDim.y + b) * C + c) * DS_Q + kq) = t;
+            } else {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) atomicAdd(dqmax + ((size_t)b * C + c) * DS_Q + kq + e, t[e]);
+                for (int e = 0; e < 4; ++e) atomicAdd(dqmax + ((size_t)b * C + c) * DS_Q + kq + e, t[e]);    // deterministic mode: one row block only
+            }
         }
     }
 }
+// In deterministic mode this entry point, which owns no workspace and whose row blocks are fixed at DS_RPB rows, refuses bags of
+// more than one row block (-1): murcl_dsmil_attn_bwd_det below is the form with a fixed summation order.
 extern "C" int murcl_dsmil_attn_bwd(const float* A, const float* dA, const float* Q, int ldq, int qcol0,
                                     const float* qmax, int B, int N, int C, float* dY, int ldy, float* dqmax,
                                     float* dots_ws, hipStream_t s) {
     if (B <= 0) return 0;
     if (C > 4 || !dots_ws) return -1;
+    const int nblk = (N + DS_RPB - 1) / DS_RPB;
+    if (nblk > 1 && murcl_deterministic()) return -1;
     hipError_t e = hipMemsetAsync(dqmax, 0, (size_t)B * C * DS_Q * 4, s);
     if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(dsmil_attn_dots_kernel, dim3(B, C), dim3(256), 0, s, A, dA, N, C, dots_ws);
     int rc = MURCL_CHECK_LAUNCH();
     if (rc) return rc;
-    hipLaunchKernelGGL(dsmil_attn_bwd_kernel, dim3((N + DS_RPB - 1) / DS_RPB, B), dim3(256), 0, s, A, dA, Q, ldq, qcol0, qmax,
+    if (nblk > 1) murcl_note_float_atomic_launch();         // the row blocks of a bag meet in dqmax through float atomics
+    hipLaunchKernelGGL(dsmil_attn_bwd_kernel<false>, dim3(nblk, B), dim3(256), 0, s, A, dA, Q, ldq, qcol0, qmax,
                        dots_ws, N, C, 1.0f / sqrtf((float)DS_Q), dY, ldy, dqmax);
     return MURCL_CHECK_LAUNCH();
+}
+// murcl_dsmil_attn_bwd with the row blocks' shares of dqmax added in a fixed order (restates the entry above: same row blocks, same
+// sums inside a block, same dY): the blocks store to ws[block][B][C][128], one reduce launch writes dqmax.  ws: at least
+// murcl_dsmil_attn_bwd_workspace bytes, 16-byte aligned; 0 bytes = one row block per bag, no workspace read.
+extern "C" long murcl_dsmil_attn_bwd_workspace(int B, int N, int C) {
+    if (B <= 0 || N <= 0 || C <= 0) return 0;
+    const int nblk = (N + DS_RPB - 1) / DS_RPB;
+    return nblk > 1 ? (long)nblk * B * C * DS_Q * 4 : 0;
+}
+extern "C" int murcl_dsmil_attn_bwd_det(const float* A, const float* dA, const float* Q, int ldq, int qcol0,
+                                        const float* qmax, int B, int N, int C, float* dY, int ldy, float* dqmax,
+                                        float* dots_ws, float* ws, long ws_bytes, hipStream_t s) {
+    if (B <= 0) return 0;
+    if (C < 1 || C > 4 || !dots_ws || N <= 0) return -1;
+    const int nblk = (N + DS_RPB - 1) / DS_RPB;
+    const long n = (long)B * C * DS_Q;
+    if (nblk > 1 && (!ws || ws_bytes < (long)nblk * n * 4 || (uintptr_t)ws % 16)) return -1;
+    if ((uintptr_t)dqmax % 16) return -1;
+    hipLaunchKernelGGL(dsmil_attn_dots_kernel, dim3(B, C), dim3(256), 0, s, A, dA, N, C, dots_ws);
+    int rc = MURCL_CHECK_LAUNCH();
+    if (rc) return rc;
+    // one row block: it is the only writer of its bag's dqmax rows - stored straight to dqmax (block 0 of a one-block "workspace")
+    hipLaunchKernelGGL(dsmil_attn_bwd_kernel<true>, dim3(nblk, B), dim3(256), 0, s, A, dA, Q, ldq, qcol0, qmax,
+                       dots_ws, N, C, 1.0f / sqrtf((float)DS_Q), dY, ldy, nblk > 1 ? ws : dqmax);
+    rc = MURCL_CHECK_LAUNCH();
+    if (rc || nblk == 1) return rc;
+    return murcl_parts_reduce(ws, dqmax, n, nblk, 0, s);
 }
 
 // Soft-max backward alone, dS = A * (dA - sum_n A dA) per (bag, class), for the reassociated path (dS then weights the rows of X:

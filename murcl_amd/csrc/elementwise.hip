@@ -190,9 +190,11 @@ extern "C" int murcl_add_lists(const MurclCopyJob* jobs_host, int n_jobs, hipStr
 // grid = (column groups of 16*CPT, row splits); a thread owns CPT = 16/sizeof(T) consecutive columns (16-byte loads)
 // for one of 16 row lanes; each block adds its partial sums atomically.  Row splits are capped at 64: float atomics
 // execute at the memory side and adders on ONE address serialise (1024 adders per column: 228 us for 134 MB).
-template <typename T>
+// PARTS (the fixed-order form, murcl_colsum_det): row split y STORES its sums to out[y * pitch + column] - plain stores, one
+// writer per element - and murcl_parts_reduce adds the splits in an order that does not depend on the run.
+template <typename T, bool PARTS = false>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, float* __restrict__ out, int R, int N, int ld,
-                                                     int rows_per_block, int overwrite) {
+                                                     int rows_per_block, int overwrite, long pitch = 0) {
     constexpr int CPT = 16 / (int)sizeof(T);
     __shared__ float red[16][16][CPT + 1];
     const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
@@ -244,36 +246,127 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, fl
             float t = 0.f;
 #pragma unroll
             for (int k = 0; k < 16; ++k) t += red[k][cl][e];
+            if constexpr (PARTS) { out[(size_t)blockIdx.y * pitch + c + e] = t; continue; }
             if (overwrite) out[c + e] = t;                     // one row split and nothing to add to: no zero-fill before the launch
             else if (gridDim.y == 1) out[c + e] += t;
-            else atomicAdd(out + c + e, t);
+            else atomicAdd(out + c + e, t);                     // row splits: never in deterministic mode (murcl_colsum keeps one)
         }
     }
 }
-extern "C" int murcl_colsum(const void* x, float* out, int R, int N, int ld, int dtype, int accumulate, hipStream_t s) {
-    if (N <= 0) return 0;
+// column groups, rows per block and row splits of a colsum launch (one split: a single writer per column)
+static void colsum_plan(int R, int N, int dtype, bool split, int& cg, int& rpb, int& gy) {
     const int bc = dtype == MURCL_DTYPE_BF16 ? 128 : 64;     // columns per block
-    const int cg = (N + bc - 1) / bc;
+    cg = (N + bc - 1) / bc;
     // bag-level row counts (<= 512) keep one writer per column: the same sum on every run (split rows meet through float
     // atomics, in arrival order); longer columns are split: ~1024 blocks, >= 32 rows each, <= 64 adders per column
-    int splits = R > 512 ? (1024 + cg - 1) / cg : 1;
+    int splits = (split && R > 512) ? (1024 + cg - 1) / cg : 1;
     if (splits > (R + 31) / 32) splits = (R + 31) / 32;
     if (splits > 64) splits = 64;
     if (splits < 1) splits = 1;
-    const int rpb = (R + splits - 1) / splits;
-    dim3 grid(cg, (R + rpb - 1) / rpb);
+    rpb = (R + splits - 1) / splits;
+    gy = (R + rpb - 1) / rpb;                                // every split has rows
+}
+// In deterministic mode this entry point, which owns no workspace, keeps ONE row split whatever R is (single writer per column);
+// murcl_colsum_det below is the split form with a fixed summation order.
+extern "C" int murcl_colsum(const void* x, float* out, int R, int N, int ld, int dtype, int accumulate, hipStream_t s) {
+    if (N <= 0) return 0;
+    if (dtype != MURCL_DTYPE_F32 && dtype != MURCL_DTYPE_BF16) return -1;
+    if (R <= 0) return accumulate ? 0 : (int)hipMemsetAsync(out, 0, (size_t)N * 4, s);     // no rows: the sums are zero
+    int cg, rpb, gy;
+    colsum_plan(R, N, dtype, !murcl_deterministic(), cg, rpb, gy);
+    dim3 grid(cg, gy);
     const int overwrite = !accumulate && grid.y == 1;
     if (!accumulate && !overwrite) {
         hipError_t e = hipMemsetAsync(out, 0, (size_t)N * 4, s);
         if (e != hipSuccess) return (int)e;
     }
+    if (grid.y > 1) murcl_note_float_atomic_launch();        // the splits of a column meet through float atomics
     if (dtype == MURCL_DTYPE_F32)
-        hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, s, (const float*)x, out, R, N, ld, rpb, overwrite);
-    else if (dtype == MURCL_DTYPE_BF16)
-        hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, out, R, N, ld, rpb, overwrite);
+        hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, s, (const float*)x, out, R, N, ld, rpb, overwrite, 0L);
     else
-        return -1;
+        hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, out, R, N, ld, rpb, overwrite, 0L);
     return MURCL_CHECK_LAUNCH();
+}
+
+// ---------------------------------------------------------------- fixed-order reduction of per-split partial results
+// out[i] (+)= sum_s part[s * np + i], i < n, np = murcl_parts_pitch(n): the second launch of every `_det` form.  A thread owns four
+// consecutive floats (16-byte loads of the partials); a workgroup takes 32 such groups, its 8 thread groups sum consecutive eighths of
+// the splits (four loads in flight, added in split order) and thread group 0 adds the 8 sums in order: the tree depends on nsplit
+// alone, never on which workgroup finished first.  One writer per output element.
+__global__ __launch_bounds__(256) void parts_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, long n, long np4,
+                                                           int nsplit, int accumulate, int vec_out) {
+    __shared__ f32x4 red[8][32];
+    const int le = threadIdx.x & 31, grp = threadIdx.x >> 5;
+    const long j = (long)blockIdx.x * 32 + le;               // group of four floats
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+    if (4 * j < n) {
+        const f32x4* p = (const f32x4*)part + j;
+        const int per = (nsplit + 7) / 8, k0 = min(nsplit, grp * per), k1 = min(nsplit, k0 + per);
+        int k = k0;
+        for (; k + 4 <= k1; k += 4) {
+            const f32x4 v0 = p[(size_t)k * np4], v1 = p[(size_t)(k + 1) * np4], v2 = p[(size_t)(k + 2) * np4], v3 = p[(size_t)(k + 3) * np4];
+            s += v0; s += v1; s += v2; s += v3;
+        }
+        for (; k < k1; ++k) s += p[(size_t)k * np4];
+    }
+    red[grp][le] = s;
+    __syncthreads();
+    if (grp == 0 && 4 * j < n) {
+        f32x4 t = red[0][le];
+#pragma unroll
+        for (int g = 1; g < 8; ++g) t += red[g][le];
+        if (vec_out) {                                       // n % 4 == 0 and out 16-byte aligned
+            f32x4* o = (f32x4*)out + j;
+            *o = accumulate ? *o + t : t;
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (4 * j + e < n) out[4 * j + e] = accumulate ? out[4 * j + e] + t[e] : t[e];
+        }
+    }
+}
+int murcl_parts_reduce(const float* part, float* out, long n, int nsplit, int accumulate, hipStream_t s) {
+    if (n <= 0 || nsplit <= 0) return 0;
+    const long np = murcl_parts_pitch(n);
+    const int vec_out = (n % 4 == 0) && ((uintptr_t)out % 16 == 0);
+    hipLaunchKernelGGL(parts_reduce_kernel, dim3((unsigned)((np / 4 + 31) / 32)), dim3(256), 0, s, part, out, n, np / 4, nsplit,
+                       accumulate, vec_out);
+    return MURCL_CHECK_LAUNCH();
+}
+
+// murcl_colsum with its row splits added in a fixed order (restates murcl_colsum above: same column groups, same row splits,
+// same sums inside a split): the splits store to ws[split][pitch], one reduce launch adds them to (or writes) out.  ws: at
+// least murcl_colsum_workspace(R, N, dtype) bytes, 16-byte aligned; 0 bytes = one split, no workspace read.
+extern "C" long murcl_colsum_workspace(int R, int N, int dtype) {
+    if (N <= 0 || R <= 0) return 0;
+    int cg, rpb, gy;
+    colsum_plan(R, N, dtype, true, cg, rpb, gy);
+    return gy > 1 ? (long)gy * murcl_parts_pitch(N) * 4 : 0;
+}
+extern "C" int murcl_colsum_det(const void* x, float* out, int R, int N, int ld, int dtype, int accumulate, float* ws, long ws_bytes,
+                                hipStream_t s) {
+    if (N <= 0) return 0;
+    if (dtype != MURCL_DTYPE_F32 && dtype != MURCL_DTYPE_BF16) return -1;
+    if (R <= 0) return accumulate ? 0 : (int)hipMemsetAsync(out, 0, (size_t)N * 4, s);     // no rows: the sums are zero
+    int cg, rpb, gy;
+    colsum_plan(R, N, dtype, true, cg, rpb, gy);
+    const long pitch = murcl_parts_pitch(N);
+    if (gy > 1 && (!ws || ws_bytes < (long)gy * pitch * 4 || (uintptr_t)ws % 16)) return -1;
+    dim3 grid(cg, gy);
+    if (gy == 1) {                                           // one split: the single-writer launch of murcl_colsum
+        if (dtype == MURCL_DTYPE_F32)
+            hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, s, (const float*)x, out, R, N, ld, rpb, !accumulate, 0L);
+        else
+            hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, out, R, N, ld, rpb, !accumulate, 0L);
+        return MURCL_CHECK_LAUNCH();
+    }
+    if (dtype == MURCL_DTYPE_F32)
+        hipLaunchKernelGGL((colsum_kernel<float, true>), grid, dim3(256), 0, s, (const float*)x, ws, R, N, ld, rpb, 0, pitch);
+    else
+        hipLaunchKernelGGL((colsum_kernel<bf16_t, true>), grid, dim3(256), 0, s, (const bf16_t*)x, ws, R, N, ld, rpb, 0, pitch);
+    const int rc = MURCL_CHECK_LAUNCH();
+    if (rc) return rc;
+    return murcl_parts_reduce(ws, out, N, gy, accumulate, s);
 }
 
 // ---------------------------------------------------------------- 1-bit ReLU' mask of an existing activation tensor

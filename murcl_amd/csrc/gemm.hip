@@ -248,6 +248,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const T* __restrict__ A, c
                 s += __shfl_xor(s, 2, 64);
                 s += __shfl_xor(s, 4, 64);
                 s += __shfl_xor(s, 8, 64);
+                // order-free: an address (wc, j, q4, r) is added to by lane (q4, r16 = 0) of exactly TWO waves (wr = 0, 1) and starts
+                // at zero - 0 + a + b and 0 + b + a are the same float - so this sum does not depend on which wave arrives first
                 if (r16 == 0) atomicAdd(&cs[wc * 64 + j * 16 + 4 * q4 + r], s);
             }
         }
@@ -370,7 +372,7 @@ __global__ __launch_bounds__(256) void gemm_nt_lds32_f32_kernel(const float* __r
                 float v = acc0[r] + acc1[r] + bv;
                 float* cp = C + (size_t)m * ldc + n;
                 if (gridDim.z > 1) {
-                    atomicAdd(cp, v);                        // 16 lanes of a quarter: 64 contiguous bytes per request
+                    atomicAdd(cp, v);                        // 16 lanes of a quarter: 64 contiguous bytes per request (never in deterministic mode: launch_skinny keeps one split)
                 } else {
                     if (mask) v = mask[(size_t)m * ldmask + n] > 0.f ? v : 0.f;      // ReLU' of the layer's saved output
                     if (relu) v = fmaxf(v, 0.f);
@@ -417,8 +419,11 @@ static int launch_skinny(const float* A, const float* B, float* C, int M, int N,
     // over K (per 256-k chunk a workgroup needs ~2 us - one DMA round trip is not covered by one chunk of MFMAs - so
     // [128 x 512 x 3072] on 64 workgroups x 12 chunks took 26 us) so that every workgroup has its whole share (two chunks) in
     // flight at once; those partial tiles meet in a zeroed C by atomics.
-    const int sp = skinny_lds_splits(M, N, K);
+    // Deterministic mode: the reduction stays unsplit (one workgroup per tile walks all of K: a single writer per element, every
+    // epilogue in the launch) - these are the few shapes the 16 x 16 form does not take, see DESIGN.md
+    const int sp = murcl_deterministic() ? 1 : skinny_lds_splits(M, N, K);
     const int kps = ((((K + SL_K - 1) / SL_K) + sp - 1) / sp) * SL_K;
+    if (sp > 1) murcl_note_float_atomic_launch();            // the K splits of a tile meet in C through float atomics
     if (sp > 1 && !accumulate) {
         hipError_t e = hipMemset2DAsync(C, (size_t)ldc * 4, 0, (size_t)N * 4, M, s);
         if (e != hipSuccess) return (int)e;
@@ -703,7 +708,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ A
                 const int n1 = n10 + wr * 64 + i * 16 + 4 * q4 + r;
                 if (n1 < N1 && n2 < N2) {
                     if (P) P[(size_t)n1 * N2 + n2] = acc[i][j][r];
-                    else atomicAdd(C + (size_t)n1 * ldc + n2, acc[i][j][r]);
+                    else atomicAdd(C + (size_t)n1 * ldc + n2, acc[i][j][r]);      // kind ATOMIC: not planned in deterministic mode
                 }
             }
         }
@@ -715,7 +720,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(const T* __restrict__ A
                 const int n1 = n10 + wr * 64 + i * 16 + 4 * q4 + r;
                 if (n1 < N1) {
                     if (part) part[(size_t)nsplit * N1 * N2 + (size_t)sp * N1 + n1] = accs[i][r];
-                    else atomicAdd(colsum_out + n1, accs[i][r]);
+                    else atomicAdd(colsum_out + n1, accs[i][r]);                  // kind ATOMIC: not planned in deterministic mode
                 }
             }
     }
@@ -929,7 +934,7 @@ __global__ __launch_bounds__(512) void gemm_tn_wide_kernel(const bf16_t* __restr
                     const int n1 = n10 + wr * 128 + ii * 16 + 4 * q4 + r;
                     const float v = a[r] + o[r];
                     if (TNW_ABLATE == 1) { if (v == 1.2345e-30f) C[0] = 1.f; continue; }
-                    atomicAdd(C + (size_t)n1 * ldc + n2, v);
+                    atomicAdd(C + (size_t)n1 * ldc + n2, v);                      // kind WIDE: not planned in deterministic mode
                 }
             }
     }
@@ -1383,6 +1388,16 @@ static_assert(TN_MAXG == MURCL_TN_MAXG, "include/murcl_amd.h");
 // ONE planner decides every product's kernel form; murcl_gemm_tn_plan reports it and murcl_gemm_tn_grouped runs it.
 typedef murcl_tn_problem TnProblem;     // include/murcl_amd.h
 struct TnStep { int kind, splits, mps; long ws_bytes; };
+extern "C" long murcl_colsum_workspace(int R, int N, int dtype);
+extern "C" int murcl_colsum_det(const void* x, float* out, int R, int N, int ld, int dtype, int accumulate, float* ws, long ws_bytes,
+                                hipStream_t s);
+// Column sums in front of a product (added to out).  Deterministic mode: the fixed-order form, its partial rows in the call's
+// workspace - they are consumed by its reduce launch before the product's kernel, next in the stream, stores its tiles there.
+static int tn_colsum(const void* x, float* out, int R, int N, int ld, int dtype, float* ws, long ws_bytes, hipStream_t stream) {
+    if (murcl_deterministic()) return murcl_colsum_det(x, out, R, N, ld, dtype, 1, ws, ws_bytes, stream);
+    return murcl_colsum(x, out, R, N, ld, dtype, 1, stream);
+}
+static inline long tn_max(long a, long b) { return a > b ? a : b; }
 
 // How product p runs on its own: kernel form, M-splits, rows per split, workspace bytes.  -1: unsupported arguments, or flags the
 // form cannot apply (only the launches that write C themselves apply them).
@@ -1395,12 +1410,17 @@ static int tn_plan_one(const TnProblem& p, int dtype, TnStep& st) {
     if (base != MURCL_DTYPE_F32 && base != MURCL_DTYPE_BF16) return -1;
     const int es = base == MURCL_DTYPE_BF16 ? 2 : 4, epc = 16 / es;
     if (p.N1 < epc || p.N2 < epc || p.N1 % epc || p.N2 % epc || (p.lda * es) % 16 || (p.ldb * es) % 16) return -1;
+    // Deterministic mode (read here, at plan / launch time): no WIDE, no ATOMIC - those products run as PARTS - and the column-sum
+    // launches in front of a product take their fixed-order form, whose partial rows share the workspace (tn_colsum)
+    const bool det = murcl_deterministic() != 0;
+    const long cs_ws = !det ? 0 : p.colsum_part ? murcl_colsum_workspace(p.colsum_rows, p.N1, MURCL_DTYPE_F32) : 0;
     TnPlan pl;
     if (tn_sq_ok(p.M, p.N1, p.N2, p.ldc, dtype) && tn_group_plan(1, &p.M, &p.N1, &p.N2, &pl, nullptr)) {
-        st = TnStep{MURCL_TN_KIND_SQUARE, pl.sp[0], pl.mps[0], pl.ws_floats * 4};
+        const long a_ws = det && p.colsum_out && !p.colsum_part ? murcl_colsum_workspace(p.M, p.N1, base) : 0;
+        st = TnStep{MURCL_TN_KIND_SQUARE, pl.sp[0], pl.mps[0], tn_max(pl.ws_floats * 4, a_ws)};
         return p.flags && p.colsum_out && !p.colsum_part ? -1 : 0;   // flags: the reduce launch, which sums colsum_part rows only
     }
-    if (dtype == MURCL_DTYPE_BF16 && p.N1 % 256 == 0 && p.N2 % 128 == 0 && p.M >= 4096) {
+    if (!det && dtype == MURCL_DTYPE_BF16 && p.N1 % 256 == 0 && p.N2 % 128 == 0 && p.M >= 4096) {
         const int tiles = (p.N1 / 256) * (p.N2 / 128);
         int sp = (256 + tiles - 1) / tiles;                // one 144 KiB-LDS workgroup per CU, splits % 8 == 0
         sp = ((sp + 7) / 8) * 8;
@@ -1415,15 +1435,18 @@ static int tn_plan_one(const TnProblem& p, int dtype, TnStep& st) {
     // the 128 x 128 ring kernel takes 55 us ([768 x 3072 x 512], tools/tn_trace.sh); up to 512 rows the small tiles win
     // (16.6 -> 12.2 us [128 x 3072 x 512], 7.7 -> 5.8 us [128 x 512 x 512], 23.7 -> 18.0 us [320 x 2048 x 512])
     if (dtype == MURCL_DTYPE_F32 && p.M <= TS_MAXM) {
-        st = TnStep{MURCL_TN_KIND_SMALL, 1, p.M, 0};
+        st = TnStep{MURCL_TN_KIND_SMALL, 1, p.M, cs_ws};
         return (p.flags & ~MURCL_TN_OVERWRITE) || (p.flags && p.colsum_part) ? -1 : 0;    // the kernel writes C, applies no factor
     }
     int splits, mps;
     tn_generic_plan(p.M, p.N1, p.N2, base, x3, splits, mps);
     // more than one split over many rows: partial tiles (+ their column sums) to the workspace, added in a fixed order.  The
     // reduce reads every split's tile, and a split without rows stores none: every split must have rows
-    if (p.M >= TN_PARTS_MIN_M && splits > 1 && (long)mps * (splits - 1) < p.M)
-        st = TnStep{MURCL_TN_KIND_PARTS, splits, mps, (long)splits * ((long)p.N1 * p.N2 + p.N1) * 4};
+    // (deterministic mode: at any row count, a single split included - its tile takes the same way - and the split count is
+    // cut to the splits that have rows)
+    if (det && (long)mps * (splits - 1) >= p.M) splits = (p.M + mps - 1) / mps;
+    if ((det || (p.M >= TN_PARTS_MIN_M && splits > 1)) && (long)mps * (splits - 1) < p.M)
+        st = TnStep{MURCL_TN_KIND_PARTS, splits, mps, tn_max((long)splits * ((long)p.N1 * p.N2 + p.N1) * 4, cs_ws)};
     else
         st = TnStep{MURCL_TN_KIND_ATOMIC, splits, mps, 0};
     return p.flags ? -1 : 0;
@@ -1451,7 +1474,11 @@ static long tn_plan(const TnProblem* pr, int n, int dtype, int* kinds, int& form
     TnPlan pl;
     if (sq && tn_group_plan(n, M, N1, N2, &pl, nullptr)) {       // (every member fits a round alone: the group fits one round)
         form = TN_SQ_GROUP;
-        ws = pl.ws_floats * 4;
+        long cs = 0;                                             // deterministic mode: the column sums of A in front of the group
+        if (murcl_deterministic())
+            for (int g = 0; g < n; ++g)
+                if (pr[g].colsum_out && !pr[g].colsum_part) cs = tn_max(cs, murcl_colsum_workspace(pr[g].M, pr[g].N1, dtype));
+        ws = tn_max(pl.ws_floats * 4, cs);
     }
     return ws;                                     // one by one: one workspace, the largest a product needs
 }
@@ -1488,12 +1515,12 @@ static int tn_small_launch(const TnProblem* pr, int n, hipStream_t stream) {
 
 // One launch of the grouped square-tile kernel + one reduce launch for n <= 4 SQUARE products; column sums of A (colsum_out
 // without colsum_part) go first, by launches of their own.
-static int tn_sq_launch(const TnProblem* pr, int n, int dtype, float* ws, hipStream_t stream) {
+static int tn_sq_launch(const TnProblem* pr, int n, int dtype, float* ws, long ws_bytes, hipStream_t stream) {
     int M[TN_MAXG], N1[TN_MAXG], N2[TN_MAXG];
     for (int g = 0; g < n; ++g) {
         M[g] = pr[g].M; N1[g] = pr[g].N1; N2[g] = pr[g].N2;
         if (pr[g].colsum_out && !pr[g].colsum_part) {
-            const int rc = murcl_colsum(pr[g].A, pr[g].colsum_out, pr[g].M, pr[g].N1, pr[g].lda, dtype, 1, stream);
+            const int rc = tn_colsum(pr[g].A, pr[g].colsum_out, pr[g].M, pr[g].N1, pr[g].lda, dtype, ws, ws_bytes, stream);
             if (rc) return rc;
         }
     }
@@ -1530,13 +1557,13 @@ static int tn_sq_launch(const TnProblem* pr, int n, int dtype, float* ws, hipStr
 }
 
 // Product p on its own, as tn_plan_one planned it.  colsum_part rows that the form cannot fold in are added up by a launch in front.
-static int tn_launch_one(TnProblem p, int dtype, float* ws, hipStream_t stream) {
+static int tn_launch_one(TnProblem p, int dtype, float* ws, long ws_bytes, hipStream_t stream) {
     TnStep st;
     tn_plan_one(p, dtype, st);
     if (st.kind == MURCL_TN_KIND_EMPTY) return 0;
-    if (st.kind == MURCL_TN_KIND_SQUARE) return tn_sq_launch(&p, 1, dtype, ws, stream);
+    if (st.kind == MURCL_TN_KIND_SQUARE) return tn_sq_launch(&p, 1, dtype, ws, ws_bytes, stream);
     if (p.colsum_part) {
-        const int rc = murcl_colsum(p.colsum_part, p.colsum_out, p.colsum_rows, p.N1, p.N1, MURCL_DTYPE_F32, 1, stream);
+        const int rc = tn_colsum(p.colsum_part, p.colsum_out, p.colsum_rows, p.N1, p.N1, MURCL_DTYPE_F32, ws, ws_bytes, stream);
         if (rc) return rc;
         p.colsum_out = nullptr;
     }
@@ -1549,6 +1576,7 @@ static int tn_launch_one(TnProblem p, int dtype, float* ws, hipStream_t stream) 
             const int rc = murcl_colsum(A, colsum_out, M, N1, lda, dtype, 1, stream);
             if (rc) return rc;
         }
+        if (splits > 1) murcl_note_float_atomic_launch();    // the M-splits of a tile meet in C through float atomics
         auto k = gemm_tn_wide_kernel;
         constexpr int LDS = 3 * 49152;
         static MurclOncePerDevice once;
@@ -1560,6 +1588,7 @@ static int tn_launch_one(TnProblem p, int dtype, float* ws, hipStream_t stream) 
     // PARTS / ATOMIC: the 128 x 128 kernel
     const bool x3 = dtype == MURCL_DTYPE_F32X3;
     float* part = st.kind == MURCL_TN_KIND_PARTS ? ws : nullptr;
+    if (!part && splits > 1) murcl_note_float_atomic_launch();     // ATOMIC: the M-splits of a tile meet in C through float atomics
     const int rows = dtype == MURCL_DTYPE_BF16 ? 64 : 32;
     const int t1 = (N1 + 127) / 128, t2 = (N2 + 127) / 128;
     dim3 grid(t1 * t2 * splits);
@@ -1595,9 +1624,9 @@ extern "C" int murcl_gemm_tn_grouped(const TnProblem* pr, int n, int dtype, floa
     const long need = tn_plan(pr, n, dtype, nullptr, form);
     if (need < 0 || (need > 0 && (!ws || ws_bytes < need))) return -1;
     if (form == TN_SMALL_GROUP) return tn_small_launch(pr, n, stream);
-    if (form == TN_SQ_GROUP) return tn_sq_launch(pr, n, dtype, ws, stream);
+    if (form == TN_SQ_GROUP) return tn_sq_launch(pr, n, dtype, ws, ws_bytes, stream);
     for (int g = 0; g < n; ++g) {
-        const int rc = tn_launch_one(pr[g], dtype, ws, stream);
+        const int rc = tn_launch_one(pr[g], dtype, ws, ws_bytes, stream);
         if (rc) return rc;
     }
     return 0;

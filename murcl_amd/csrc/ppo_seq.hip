@@ -258,13 +258,47 @@ extern "C" int murcl_ppo_act(const float* const* params, int S, int H, int K, co
     return MURCL_CHECK_LAUNCH();
 }
 
-extern "C" long murcl_ppo_epoch_workspace(int T, int B, int S, int H) {
+// the epoch's weight gradients (+ the bias gradients that ride along) as murcl_gemm_tn_grouped takes them; pointers may be NULL (plan only)
+static int ps_wgrad_problems(murcl_tn_problem* pr, int T, int B, int S, int H, const float* de1, const float* states, const float* de2,
+                             const float* e1, const float* dgi, const float* e2, const float* dgh1, const float* hs, float* const* grads) {
+    const int R = T * B;
+    int np = 0;
+    auto add = [&](const float* A_, const float* B_, float* C_, float* cs, int M_, int N1_, int N2_) {
+        murcl_tn_problem& q = pr[np++];
+        q.A = A_; q.B = B_; q.C = C_; q.colsum_part = nullptr; q.colsum_out = cs;
+        q.M = M_; q.N1 = N1_; q.N2 = N2_; q.lda = N1_; q.ldb = N2_; q.ldc = N2_; q.colsum_rows = 0; q.flags = 0; q.scale = 1.f;
+    };
+    add(de1, states, grads ? grads[P_W1] : nullptr, grads ? grads[P_B1] : nullptr, R, PS_E1, S);
+    add(de2, e1, grads ? grads[P_W2] : nullptr, grads ? grads[P_B2] : nullptr, R, H, PS_E1);
+    add(dgi, e2, grads ? grads[P_WIH] : nullptr, grads ? grads[P_BIH] : nullptr, R, 3 * H, H);
+    if (T > 1) add(dgh1, hs, grads ? grads[P_WHH] : nullptr, nullptr, R - B, 3 * H, H);
+    return np;
+}
+// floats of the epoch's own buffers, rounded up to 16 bytes: where the tail below starts
+static long ps_epoch_floats(int T, int B, int H) {
     const long R = (long)T * B;
-    if (R <= 0) return 0;
     long f = R * (2L * PS_E1 + 2L * H + 5L * 3 * H + 2L * H + (PS_MAXK + 1) + 1);   // e1,de1 | e2,de2 | gi,gh,gates,dgi,dgh | hs,dhs | dzv | lossrow
     f += (long)B * H;                                                                 // dhp (unused tail of the recurrence)
     f += 2L * H * 3 * H + (long)PS_E1 * H;                                            // W_ih^T, W_hh^T, W_2^T
-    return f * 4;
+    return f;
+}
+// Bytes behind the epoch's own buffers for what the weight gradients and the column sums of dgh need as a workspace.  By default
+// none (rollouts beyond 512 rows plan as ATOMIC); in deterministic mode the planner's PARTS tiles and murcl_colsum_det's partial
+// rows - one region for both, they run one after the other in the stream.  < 0: the planner refuses the shapes.
+static long ps_epoch_tail_bytes(int T, int B, int S, int H) {
+    murcl_tn_problem pr[4];
+    const int np = ps_wgrad_problems(pr, T, B, S, H, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    const long tn = murcl_gemm_tn_plan(pr, np, MURCL_F32, nullptr);
+    if (tn < 0) return tn;
+    const long cs = murcl_deterministic() ? murcl_colsum_workspace(T * B, 3 * H, MURCL_F32) : 0;
+    return tn > cs ? tn : cs;
+}
+extern "C" long murcl_ppo_epoch_workspace(int T, int B, int S, int H) {
+    const long R = (long)T * B;
+    if (R <= 0) return 0;
+    const long f = ps_epoch_floats(T, B, H);
+    const long tail = S > 0 && H > 0 ? ps_epoch_tail_bytes(T, B, S, H) : 0;
+    return tail > 0 ? ((f + 3) & ~3L) * 4 + tail : f * 4;       // (read at call time: the mode decides whether there is a tail)
 }
 
 // One epoch of PPO.update (rlmil.py:169-181) minus the optimizer step: forward of evaluate() over the rollout
@@ -301,6 +335,10 @@ static int ps_epoch(const float* const* params, float* const* grads, const float
     const float* whh_t = wt ? wt[1] : whh_ws;
     const float* w2_t = wt ? wt[2] : w2_ws;
     const size_t bh = (size_t)B * H, b3 = (size_t)B * 3 * H;
+    // the workspace of the weight gradients and of the fixed-order column sums, behind the epoch's buffers (deterministic mode only)
+    const long tail_bytes = ps_epoch_tail_bytes(T, B, S, H);
+    if (tail_bytes < 0) return -1;
+    float* tail = tail_bytes ? ws + ((ps_epoch_floats(T, B, H) + 3) & ~3L) : nullptr;
 
     const bool fused = murcl_gru_step_supported(B, H, 0);    // one launch per GRU time step and direction
     // ---------------- forward (rlmil.py:103-112)
@@ -355,7 +393,10 @@ static int ps_epoch(const float* const* params, float* const* grads, const float
             }
         }
     }
-    PS_CHECK(murcl_colsum(dgh, grads[P_BHH], R, 3 * H, 3 * H, MURCL_F32, 1, stream));
+    if (murcl_deterministic())      // rollouts beyond 512 rows: the row splits' partial sums added in a fixed order
+        PS_CHECK(murcl_colsum_det(dgh, grads[P_BHH], R, 3 * H, 3 * H, MURCL_F32, 1, tail, tail_bytes, stream));
+    else
+        PS_CHECK(murcl_colsum(dgh, grads[P_BHH], R, 3 * H, 3 * H, MURCL_F32, 1, stream));
     // the two encoder dgrads with ReLU' (the layer's saved output > 0) in the epilogue
     PS_CHECK(murcl_gemm_nt(dgi, wih_t, de2, R, H, 3 * H, 3 * H, 3 * H, H, MURCL_F32, MURCL_F32, MURCL_EPI_MASK, nullptr, e2, H, nullptr,
                            nullptr, 0, nullptr, 0, stream));
@@ -363,17 +404,8 @@ static int ps_epoch(const float* const* params, float* const* grads, const float
                            nullptr, 0, nullptr, 0, stream));
     // every weight gradient (+ the bias gradients that are column sums of its left operand) added in ONE launch
     murcl_tn_problem pr[4];
-    int np = 0;
-    auto add = [&](const float* A_, const float* B_, float* C_, float* cs, int M_, int N1_, int N2_) {
-        murcl_tn_problem& q = pr[np++];
-        q.A = A_; q.B = B_; q.C = C_; q.colsum_part = nullptr; q.colsum_out = cs;
-        q.M = M_; q.N1 = N1_; q.N2 = N2_; q.lda = N1_; q.ldb = N2_; q.ldc = N2_; q.colsum_rows = 0; q.flags = 0; q.scale = 1.f;
-    };
-    add(de1, states, grads[P_W1], grads[P_B1], R, PS_E1, S);
-    add(de2, e1, grads[P_W2], grads[P_B2], R, H, PS_E1);
-    add(dgi, e2, grads[P_WIH], grads[P_BIH], R, 3 * H, H);
-    if (T > 1) add(dgh + b3, hs, grads[P_WHH], nullptr, R - B, 3 * H, H);
-    PS_CHECK(murcl_gemm_tn_grouped(pr, np, MURCL_F32, nullptr, 0, stream));
+    const int np = ps_wgrad_problems(pr, T, B, S, H, de1, states, de2, e1, dgi, e2, dgh + b3, hs, grads);
+    PS_CHECK(murcl_gemm_tn_grouped(pr, np, MURCL_F32, tail, tail_bytes, stream));
     return 0;
 }
 

@@ -9,6 +9,7 @@
 // collectives with its backward sets 256 - (reserved CUs), so that the channels find free CUs and the round still fits
 // (costs budget/256 of the rate of those kernels, always; reference side: nn.DataParallel, train_MuRCL.py:145).
 #include "common.h"
+#include <atomic>
 
 static int g_cu_budget = 256;
 
@@ -21,6 +22,22 @@ extern "C" int murcl_set_cu_budget(int cus) {
     g_cu_budget = cus & ~7;
     return g_cu_budget;
 }
+
+// ---------------------------------------------------------------- deterministic mode
+// Process-wide, off by default.  Launchers and planners read it when they launch (a captured graph keeps whichever form was
+// captured): while it is on, no launcher of this library picks a kernel form in which several workgroups add floats into one
+// address in arrival order.  The `_det` entry points (caller-owned workspace: per-split partial results, then one reduce launch
+// with a fixed summation tree - murcl_parts_reduce, elementwise.hip) are the fast fixed-order forms; an entry point that owns no
+// workspace runs its single-writer form instead (one split), or refuses (-1) where it has none.
+static std::atomic<int> g_deterministic{0};
+static std::atomic<long> g_float_atomic_launches{0};
+
+extern "C" int murcl_set_deterministic(int on) { return g_deterministic.exchange(on ? 1 : 0); }      // -> the previous state
+extern "C" int murcl_deterministic(void) { return g_deterministic.load(std::memory_order_relaxed); }
+// launches so far of a form whose float result depends on the order in which workgroups arrive (host counter; every launcher
+// that picks such a form counts it): what shows that a shape reaches such a form by default, and that the mode removes it
+extern "C" long murcl_float_atomic_launches(void) { return g_float_atomic_launches.load(std::memory_order_relaxed); }
+void murcl_note_float_atomic_launch(void) { g_float_atomic_launches.fetch_add(1, std::memory_order_relaxed); }
 
 // ---------------------------------------------------------------- box calibration (bench.py's `box` block, round 6)
 // Boxes of one MI355X pool differ by a few per cent in the clocks they hold (the same tree read 45.2 k and 42.7 k bags/s on

@@ -97,6 +97,21 @@ def _c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def deterministic():
+    """Is deterministic mode on (murcl_amd.set_deterministic)?  Read at every launch: the wrappers below then call the fixed-order
+    ``_det`` entry points with a workspace from the caching allocator."""
+    return bool(_lib.lib().murcl_deterministic())
+
+
+def float_atomic_launches():
+    """Launches so far of a kernel form whose float result depends on workgroup arrival order (murcl_float_atomic_launches)."""
+    return int(_lib.lib().murcl_float_atomic_launches())
+
+
+def _det_ws(nbytes, device):
+    return torch.empty((nbytes // 4,), dtype=torch.float32, device=device) if nbytes else None
+
+
 F32X3 = 2          # GEMM dtype code: f32 tensors, products as a 3-term bf16 split on the bf16 matrix pipe (include/murcl_amd.h)
 
 
@@ -900,7 +915,13 @@ def colsum(x, out=None, accumulate=False):
     R, N = x.shape
     if out is None:
         out = torch.empty((N,), dtype=torch.float32, device=x.device)
-    check(_lib.lib().murcl_colsum(ptr(x), ptr(out), R, N, N, dt(x), int(accumulate), stream()), "colsum")
+    L = _lib.lib()
+    if L.murcl_deterministic():
+        wsb = L.murcl_colsum_workspace(R, N, dt(x))
+        ws = _det_ws(wsb, x.device)
+        check(L.murcl_colsum_det(ptr(x), ptr(out), R, N, N, dt(x), int(accumulate), ptr(ws), wsb, stream()), "colsum_det")
+        return out
+    check(L.murcl_colsum(ptr(x), ptr(out), R, N, N, dt(x), int(accumulate), stream()), "colsum")
     return out
 
 
@@ -1180,6 +1201,17 @@ def weighted_rowsum(X, A, into=None):
     if C > 4 and into is None:
         return torch.cat([weighted_rowsum(X, A[:, :, a:b]) for a, b in _class_groups(C)], 1)
     X, A = _c(X), _c(A)
+    L = _lib.lib()
+    if L.murcl_deterministic() and not (into is None and B == 1 and N >= 1 << 16 and N % 64 == 0):
+        # the fixed-order form: the row splits store to a workspace, one reduce launch adds them (to ``into``, or writes Z)
+        Z = into if into is not None else torch.empty((B, C, d), dtype=torch.float32, device=X.device)
+        assert Z.is_contiguous() and Z.dtype == torch.float32 and Z.numel() == B * C * d
+        wsb = L.murcl_weighted_rowsum_workspace(B, N, d, C)
+        ws = _det_ws(wsb, X.device)
+        with _span(lambda: (f"weighted_rowsum_det<{_DT_NAME[X.dtype]}>", dict(bytes=X.numel() * X.element_size(), flops=2.0 * B * N * d * C))):
+            check(L.murcl_weighted_rowsum_det(ptr(X), ptr(A), ptr(Z), B, N, d, C, dt(X), int(into is not None), ptr(ws), wsb, stream()),
+                  "weighted_rowsum_det")
+        return Z.view(B, C, d)
     if into is not None:
         assert into.is_contiguous() and into.dtype == torch.float32 and into.numel() == B * C * d
         with _span(lambda: (f"weighted_rowsum<{_DT_NAME[X.dtype]}>", dict(bytes=X.numel() * X.element_size(), flops=2.0 * B * N * d * C))):
@@ -1243,8 +1275,15 @@ def dsmil_attn_bwd(A, dA, Y, qcol0, qmax, dY, B, N, C):
         return torch.cat(parts, 1).view(B * C, -1)
     dqmax = torch.empty((B * C, qmax.shape[1]), dtype=torch.float32, device=Y.device)
     dots = torch.empty((B * C,), dtype=torch.float32, device=Y.device)
-    check(_lib.lib().murcl_dsmil_attn_bwd(ptr(A), ptr(_c(dA)), ptr(Y), Y.stride(0), qcol0, ptr(qmax), B, N, C, ptr(dY),
-                                          dY.stride(0), ptr(dqmax), ptr(dots), stream()), "dsmil_attn_bwd")
+    L = _lib.lib()
+    if L.murcl_deterministic():
+        wsb = L.murcl_dsmil_attn_bwd_workspace(B, N, C)
+        ws = _det_ws(wsb, Y.device)
+        check(L.murcl_dsmil_attn_bwd_det(ptr(A), ptr(_c(dA)), ptr(Y), Y.stride(0), qcol0, ptr(qmax), B, N, C, ptr(dY),
+                                         dY.stride(0), ptr(dqmax), ptr(dots), ptr(ws), wsb, stream()), "dsmil_attn_bwd_det")
+        return dqmax
+    check(L.murcl_dsmil_attn_bwd(ptr(A), ptr(_c(dA)), ptr(Y), Y.stride(0), qcol0, ptr(qmax), B, N, C, ptr(dY),
+                                 dY.stride(0), ptr(dqmax), ptr(dots), stream()), "dsmil_attn_bwd")
     return dqmax
 
 
