@@ -573,6 +573,21 @@ int murcl_sgd_step(float* p, float* g, float* buf, long n, float lr, float momen
 long murcl_kmeans_workspace_bytes(int N, int d, int K);
 int murcl_kmeans_step(const float* X, int N, int d, int K, float* centers, int* labels, int* counts, float* stats,
                       float* mind2, int update, void* workspace, murcl_stream_t stream);
+/* The same step for any feature width and up to 64 clusters (a ResNet-50 / VGG-16 extractor's 2048 / 4096 columns, 384 / 768 /
+ * 1280-wide transformer features; --num_clusters above 16): d any positive multiple of 32, 1 <= K <= 64, else -1 with no launch.
+ * Same arguments, outputs, tie rule (first minimum) and empty-cluster rule (keeps its centre) as murcl_kmeans_step; the work is
+ * tiled over d (cross terms C . X^T on the exact-f32 bag-level product with its reduction unsplit, a label launch, 512-column
+ * slab sums in row order, the same fixed-order reduction), so the sums are added in another order than murcl_kmeans_step's: equal
+ * to rounding, not bit for bit.  Deterministic in either mode: no float atomics, murcl_float_atomic_launches does not move.
+ * workspace: murcl_kmeans_wide_workspace_bytes(N, d, K) (-1 for a shape the entry refuses), 16-byte aligned. */
+long murcl_kmeans_wide_workspace_bytes(int N, int d, int K);
+int murcl_kmeans_step_wide(const float* X, int N, int d, int K, float* centers, int* labels, int* counts, float* stats,
+                           float* mind2, int update, void* workspace, murcl_stream_t stream);
+/* The cross terms of k-means and of its k-means++ seeding (scikit-learn's _kmeans_plusplus behind KMeans.fit,
+ * features_clustering.py:11): out [R,N] = rows [R,d] . X [N,d]^T, f32 on the exact-f32 matrix pipe, 1 <= R <= 1024, d a positive
+ * multiple of 32 (else -1).  murcl_gemm_nt's bag-level form with its reduction kept unsplit whatever the deterministic mode (which is
+ * not read): one writer per element, so a seeding picks the same centres on every run, on small slides of d >= 1536 too. */
+int murcl_kmeans_cross(const float* rows, int R, const float* X, int N, int d, float* out, murcl_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -406,7 +406,8 @@ int murcl_nt_t16_launch(const float* A, const float* B, float* C, int M, int N, 
 constexpr int NT_T16_FEW_TILES = 64;       // products of at most this many 32 x 32 tiles (= 256 of the 16 x 16 kind: one round) ...
 constexpr int NT_T16_MIN_CHUNKS = 2;       // ... with at least this many 256-k chunks take the 16 x 16 form ([128 x 512 x 512]: 7.2 -> 4.8 us; at 128 tiles it loses: profiles/r04_w_*)
 static int launch_skinny(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc,
-                         int epi, const float* bias, int accumulate, hipStream_t s, const float* mask = nullptr, int ldmask = 0) {
+                         int epi, const float* bias, int accumulate, hipStream_t s, const float* mask = nullptr, int ldmask = 0,
+                         bool unsplit = false) {
     // few outputs, long reduction - the shapes the LDS form below would split over K (zero-fill + atomics + a ReLU launch): 16 x 16
     // tiles with the K range split over the waves of one workgroup instead, everything in one launch
     // (also a handful of tiles with three or more chunks each: [128 x 128 x 1024] is 16 workgroups walking 4 chunks, or 64 with all four in flight)
@@ -421,7 +422,8 @@ static int launch_skinny(const float* A, const float* B, float* C, int M, int N,
     // flight at once; those partial tiles meet in a zeroed C by atomics.
     // Deterministic mode: the reduction stays unsplit (one workgroup per tile walks all of K: a single writer per element, every
     // epilogue in the launch) - these are the few shapes the 16 x 16 form does not take, see DESIGN.md
-    const int sp = murcl_deterministic() ? 1 : skinny_lds_splits(M, N, K);
+    // (`unsplit`: the same on request, for a caller whose result must not depend on the mode - murcl_nt_f32_unsplit below)
+    const int sp = (unsplit || murcl_deterministic()) ? 1 : skinny_lds_splits(M, N, K);
     const int kps = ((((K + SL_K - 1) / SL_K) + sp - 1) / sp) * SL_K;
     if (sp > 1) murcl_note_float_atomic_launch();            // the K splits of a tile meet in C through float atomics
     if (sp > 1 && !accumulate) {
@@ -447,6 +449,13 @@ static int launch_skinny(const float* A, const float* B, float* C, int M, int N,
         rc = MURCL_CHECK_LAUNCH();
     }
     return rc;
+}
+
+// kmeans.hip (murcl_kmeans_step_wide: the cross terms C . X^T, centres as the short side): the bag-level f32 product with a single
+// writer per element in either mode - the 16 x 16 form where it applies, else the LDS form with its reduction unsplit
+int murcl_nt_f32_unsplit(const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, hipStream_t s) {
+    if (M <= 0 || M > 1024 || N <= 0 || K <= 0 || K % 32 || lda % 4 || ldb % 4) return -1;
+    return launch_skinny(A, B, C, M, N, K, lda, ldb, ldc, EPI_NONE, nullptr, 0, s, nullptr, 0, true);
 }
 
 // C-ABI: see include/murcl_amd.h

@@ -3,8 +3,10 @@
 ``clustering(feats, num_clusters)`` / ``save_to_json(indices, num_clusters)`` keep the reference's signatures and file
 formats (``features_cluster_indices`` ``[N,1]`` in an npz; a json list of ``num_clusters`` ascending patch-id lists - the
 input of ``WSIWithCluster``).  The reference runs scikit-learn's KMeans(random_state=985) on the host, about a second
-per slide; here Lloyd's iterations run on the HIP kernel (one pass over the slide's features per iteration, no float
-atomics, so a run is reproducible bit for bit).  scikit-learn's random stream cannot be reproduced, so the partitions are
+per slide; here Lloyd's iterations run on the HIP kernels, without float atomics, so a run is reproducible bit for bit:
+``murcl_kmeans_step`` (one pass over the slide's features per iteration) for d in 256 / 512 / 1024 with at most 16 clusters,
+``murcl_kmeans_step_wide`` (the same step tiled over d) for every other width - 2048 and 4096 of the reference's ResNet-50 /
+VGG-16 extractors, 384 / 768 / 1280 ... - and up to 64 clusters.  scikit-learn's random stream cannot be reproduced, so the partitions are
 not the reference's label for label; what is pinned (tests) is that from the SAME initial centres the iterations are
 scikit-learn's Lloyd iterations (same labels, centres and inertia), and that k-means++ seeding + restarts reach the
 same inertia range.
@@ -14,14 +16,21 @@ import json
 import numpy as np
 import torch
 
-from .. import _lib, ops
+from .. import _lib
 from .._lib import check, ptr, stream
+
+
+def _narrow(d, K):
+    """Does ``murcl_kmeans_step`` take this shape?  (Those shapes keep that kernel - and their bits.)"""
+    return d in (256, 512, 1024) and 1 <= K <= 16
 
 
 def _step(X, centers, labels, counts, stats, mind2, ws, update):
     N, d = X.shape
-    check(_lib.lib().murcl_kmeans_step(ptr(X), N, d, centers.shape[0], ptr(centers), ptr(labels), ptr(counts), ptr(stats),
-                                       ptr(mind2), int(update), ptr(ws), stream()), "kmeans_step")
+    K = centers.shape[0]
+    fn, name = ((_lib.lib().murcl_kmeans_step, "kmeans_step") if _narrow(d, K) else
+                (_lib.lib().murcl_kmeans_step_wide, "kmeans_step_wide"))
+    check(fn(ptr(X), N, d, K, ptr(centers), ptr(labels), ptr(counts), ptr(stats), ptr(mind2), int(update), ptr(ws), stream()), name)
 
 
 def _relocate_empty(X, centers, labels, mind2, n):
@@ -44,20 +53,29 @@ def lloyd(X, centers, max_iter=300, tol=1e-4):
     """Lloyd's algorithm from the given centres, with scikit-learn's conventions (what the reference's KMeans call runs):
     stop when no label changes, or when the squared centre shift falls to ``tol * mean feature variance``, or after
     ``max_iter`` iterations; empty clusters are relocated; final labels / inertia are those of the final centres.
-    X [N,d] f32 cuda (d in 256/512/1024), centers [K,d] (K <= 16).
+    X [N,d] f32 cuda, any d, centers [K,d] with K <= 64.  d in 256/512/1024 with K <= 16 runs on ``murcl_kmeans_step``, every other
+    shape on ``murcl_kmeans_step_wide``; a d that is no multiple of 32 is padded once with zero columns (they change no distance
+    and no mean) and the returned centres carry the caller's d columns.
     -> (labels int32 [N], centers [K,d], inertia float, iterations)."""
     if not X.is_cuda:
         raise RuntimeError("murcl_amd k-means runs on the GPU only (no CPU fallback)")
     X = X.float().contiguous()
-    N, d = X.shape
+    N, d0 = X.shape
     centers = centers.to(X.device, torch.float32).contiguous().clone()
     K = centers.shape[0]
+    if not 1 <= K <= 64 or N < 1 or d0 < 1 or centers.shape[1] != d0:
+        raise ValueError(f"k-means takes 1..64 clusters and centres of the features' width (got X {tuple(X.shape)}, centres {tuple(centers.shape)})")
+    thresh = tol * float(X.var(0, unbiased=False).mean())             # on the caller's columns: zero pad columns would lower the mean
+    if d0 % 32:
+        X = torch.nn.functional.pad(X, (0, 32 - d0 % 32)).contiguous()
+        centers = torch.nn.functional.pad(centers, (0, 32 - d0 % 32)).contiguous()
+    d = X.shape[1]
     labels = torch.full((N,), -1, dtype=torch.int32, device=X.device)
     counts = torch.empty((K,), dtype=torch.int32, device=X.device)
     mind2 = torch.empty((N,), dtype=torch.float32, device=X.device)
     stats = torch.zeros((3 + K,), dtype=torch.float32, device=X.device)
-    ws = torch.empty((_lib.lib().murcl_kmeans_workspace_bytes(N, d, K) + 3) // 4, dtype=torch.float32, device=X.device)
-    thresh = tol * float(X.var(0, unbiased=False).mean())
+    ws_bytes = (_lib.lib().murcl_kmeans_workspace_bytes if _narrow(d, K) else _lib.lib().murcl_kmeans_wide_workspace_bytes)(N, d, K)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=X.device)
     it = 0
     while it < max_iter:
         prev = centers.clone()
@@ -71,7 +89,7 @@ def lloyd(X, centers, max_iter=300, tol=1e-4):
         if h[2] == 0 or shift <= thresh:              # no label moved (strict convergence), or the centres stopped moving
             break
     _step(X, centers, labels, counts, stats, mind2, ws, False)       # labels and inertia against the final centres
-    return labels, centers, float(stats[1].item()), it
+    return labels, (centers[:, :d0].contiguous() if d != d0 else centers), float(stats[1].item()), it
 
 
 def kmeans_plusplus(X, K, generator):
@@ -80,11 +98,17 @@ def kmeans_plusplus(X, K, generator):
     N, d = X.shape
     trials = 2 + int(np.log(K))
     if d % 32:                                                # the GEMM's reduction runs in 128-byte slabs: zero columns change no distance
-        X = torch.nn.functional.pad(X, (0, 32 - d % 32)).contiguous()
+        X = torch.nn.functional.pad(X, (0, 32 - d % 32))
+    X = X.contiguous()
 
     def cross(rows):
-        """rows [r, d] . X^T -> [r, N] on the repo's own f32 GEMM (exact-f32 MFMA), not a library matmul."""
-        return ops.gemm_nt(rows.contiguous(), X)
+        """rows [r, d] . X^T -> [r, N] on the repo's own f32 GEMM (exact-f32 MFMA), not a library matmul: ``murcl_kmeans_cross``, the
+        bag-level form of ``ops.gemm_nt`` with its reduction unsplit in either mode (on a small slide of d >= 1536 the default form
+        splits it into a zeroed C - float atomics, arrival order - and the seeding must pick the same centres on every run)."""
+        rows = rows.contiguous()
+        out = torch.empty((rows.shape[0], N), dtype=torch.float32, device=X.device)
+        check(_lib.lib().murcl_kmeans_cross(ptr(rows), rows.shape[0], ptr(X), N, X.shape[1], ptr(out), stream()), "kmeans_cross")
+        return out
 
     xx = (X * X).sum(1)
     first = int(torch.randint(N, (1,), generator=generator, device=X.device).item())
