@@ -582,6 +582,34 @@ def dsmil_route(B, N, d, C, dropped):
     return DSMILRoute(reassoc, qv, stream)
 
 
+CLAMRoute = collections.namedtuple("CLAMRoute", "fc_panel fc_bits drop gate dz1_panel inst_fused")
+
+
+def clam_route(B, N, d, L, D, dtype, gated, keeps, grad_on, needs_grad, inst=None):
+    """Which form every stage of a CLAM call takes (``CLAMFn`` describes them).  ``keeps``: None, "seeds" or "tensors"; ``grad_on``: the
+    caller's grad mode, ``needs_grad``: some input requires a gradient (both: a backward may follow); ``inst``: None or (n_cls, k_sample, is the
+    loss the caller's own).  Not memoised: the parity tests flip the module switches between two calls of one shape; cheap terms come first."""
+    rows, bf16, GW, backward = B * N, dtype == torch.bfloat16, (2 * D if gated else D), bool(grad_on and needs_grad)
+    fc_panel = bf16 and d == 512 and ops.panel_supported(rows, L, 512, ops.PG_BIAS_RELU)
+    drop = None if keeps is None else "injected" if keeps == "tensors" else "epilogue" if (fc_panel and _FUSED_FC_DROP) else \
+        "bitmask" if (rows % 32 == 0 and L % 128 == 0) else "mask"
+    fc_bits = fc_panel and (drop == "epilogue" or (keeps is None and grad_on))      # that epilogue leaves the 1-bit ReLU mask
+    panel = bf16 and L == 512 and ops.panel_supported(rows, GW, 512, ops.PG_BIAS)
+    epilogue = panel and gated and GW == 512                # the shapes whose score can come out of the gate GEMM's epilogue
+    if _FUSED_GATE and epilogue and keeps is None and not backward and ops.panel_supported(rows, GW, 512, ops.PG_GATE):
+        gate = "fused"
+    elif (_GATE_U and epilogue and keeps != "tensors" and ops.panel_supported(rows, GW, 512, ops.PG_GATE_U)
+          and ops.gated_bwd_il_supported(rows, D, L, N) and ops.panel_supported(rows, L, 512, ops.PG_RANK1_MASK, N)):
+        gate = "u"
+    else:
+        gate = "panel" if panel else "tile"
+    dz1_panel = gate == "u" or (backward and bf16 and GW == 512 and ops.panel_supported(rows, L, 512, ops.PG_RANK1_MASK, N))
+    inst_fused = inst is not None and not inst[2] and _FUSED_INST and 2 * inst[0] <= 16 and inst[1] <= 32 and L % 8 == 0
+    assert D % 16 == 0 or gate in ("panel", "tile")         # (the epilogue gates read the interleaved weight views of ``ops.clam_views``)
+    assert dz1_panel or gate != "u"                         # (its backward may group the weight gradients: column sums deferred by the panel dz1 product)
+    return CLAMRoute(fc_panel, fc_bits, drop, gate, dz1_panel, inst_fused)
+
+
 class EncoderSession:
     """ONE aggregator backward for the T patch steps of a sequential training step (train_MuRCL.py:233-304 at train_stage 3).
 
@@ -1096,164 +1124,211 @@ class StackParamsFn(torch.autograd.Function):
         return (None, *gw, *gb)
 
 
-class CLAMFn(torch.autograd.Function):
-    """CLAM_SB.bag_forward for a batch of equal-length bags, optionally with the instance-level loss
-    (models/clam.py:134-181,103-132).
+CLAMInstFused = collections.namedtuple("CLAMInstFused", "ids dl w_st k n_cls")                  # what each form of CLAM's instance
+CLAMInstExplicit = collections.namedtuple("CLAMInstExplicit", "rows feats dl scale k n_cls")    # branch keeps for its backward
 
-    x [B,N,d] in the compute dtype; parameters f32.  ``keeps`` = None (eval) or the three dropout keep-multiplier
-    tensors (values 0 or 1/0.75) for h, the tanh branch and the sigmoid branch (clam.py:71-72,47-48).
-    ``inst`` = None or (W [n_cls,2,512], b [n_cls,2], labels: list[int], k_sample, subtyping).
-    Returns (M [B,512], A [B,N], raw scores [B,N], inst_loss [B], ids [B,2k], preds/targets [2,B,n_cls,2k]); only M and
-    inst_loss carry grad.
-    """
+
+def _clam_first_layer(route, x2, w1c, b1, k1):
+    """h = Dropout(ReLU(x W1^T + b1)) (clam.py:69-72) -> (h, m1): m1 = the 1-bit mask of h > 0 for the panel dz1 product, or None."""
+    if route.fc_panel:
+        # weight-stationary panel kernel; its 1-bit ReLU mask also serves the backward pass.  Seeded Dropout(0.25) behind the ReLU
+        # happens in the same epilogue: the mask is never materialised and the bits record what survives
+        h, m1, _ = ops.panel_gemm(x2, w1c, ops.PG_BIAS_RELU, bias=b1, want_bitmask=route.fc_bits, drop=k1 if route.drop == "epilogue" else None)
+    else:
+        h, m1 = ops.gemm_nt(x2, w1c, epi=ops.EPI_BIAS_RELU, bias=b1), None
+    if route.drop == "bitmask":
+        # the mask is generated inside the pass that applies it, which also leaves the 1-bit mask of the surviving positive entries (bf16 panel dgrad)
+        m1 = ops.dropout_relu_bitmask(h, k1, want_bits=h.dtype == torch.bfloat16)
+    elif route.drop in ("mask", "injected"):                                       # a materialised mask; a keep mask from the caller (parity tests)
+        ops.mul(h, k1 if route.drop == "injected" else ops.dropout_mask(h.shape, h.dtype, k1.keep_p, h.device, seed=k1.seed))
+    return h, m1
+
+
+def _clam_gate(route, h, B, N, gate_params, views, c, ka, kb):
+    """Attention scores, soft-max over the bag and pooling (clam.py:18-56,144,170) -> (U or None, s [B,N], A [B,N], M [B,L])."""
+    wa, ba, wb, bb, wc, bc = gate_params
+    gated, L = wb is not None, h.shape[1]
+    if route.gate in ("fused", "u"):
+        # fused - forward-only calls (validation, heat-map scoring, the frozen aggregator of stage 2): the score comes out of the gate
+        # GEMM's epilogue - tanh(a_d) sigmoid(b_d) c_d summed per wave - and the [B*N, 2D] pre-activations are never written
+        # u - calls a backward pass may follow: the same epilogue also leaves the pre-activations (interleaved column order) for it,
+        # and the separate score pass over U (97-120 us at C3) disappears; the gate Dropouts are applied inside from their seeds
+        U, s_parts = (None, ops.panel_gate_score(h, views[1], views[3], views[4], bc, parts=True)) if route.gate == "fused" else \
+            ops.panel_gate_u(h, views[1], views[3], views[4], bc, ka, kb, parts=True)
+        # the epilogue's partial rows summed on the way, and the pooled rows cleared for the pass below: one launch
+        M = torch.empty((B, L), dtype=torch.float32, device=h.device)
+        s, A = ops.softmax_rows_parts(s_parts, B, N, zero=M)
+        ops.weighted_rowsum(h.view(B, N, L), A.view(B, N, 1), into=M)
+        return U, s, A, M
+    wab, bab = (torch.cat([wa, wb], 0), torch.cat([ba, bb], 0)) if gated else (wa, ba)           # both gate branches, one pass
+    if route.gate == "panel":        # bf16 with 512-wide h: the weight-stationary panel kernel (same GEMM, half the time of the tile kernel)
+        U, _, _ = ops.panel_gemm(h, c(wab), ops.PG_BIAS, bias=bab)
+    else:
+        U = ops.gemm_nt(h, c(wab), epi=ops.EPI_BIAS, bias=bab)
+    s = ops.gated_score_fwd(U, wc.reshape(-1).contiguous(), bc, ka, kb, gated=gated).view(B, N)
+    A = ops.softmax_rows(s)
+    return U, s, A, ops.weighted_rowsum(h.view(B, N, L), A.view(B, N, 1)).view(B, L)
+
+
+def _clam_custom_inst_loss(custom_loss, logits_g, targets):
+    """The reference hands (logits [rows,2], targets [rows]) of every evaluated (bag, class) pair to whatever loss it was constructed with
+    (clam.py:118,131).  The gather, the classifier product and the predictions are the HIP kernels; the caller's loss runs on the pair's few
+    logits as given (rows with target -1 do not exist for that pair) and its gradient w.r.t. them - taken here with autograd on that leaf - takes
+    the place of the cross-entropy gradient in the backward pass.  A loss with parameters of its own gets no gradient for them.  -> (loss [B*n_cls], dlogits [B*n_cls*2k, 2])"""
+    B, n_cls = targets.shape[:2]
+    with torch.enable_grad():
+        leaf = logits_g.detach().requires_grad_()
+        pair = []
+        for b_ in range(B):
+            for c_ in range(n_cls):
+                keep_rows = targets[b_, c_] >= 0
+                pair.append(custom_loss(leaf[b_, c_][keep_rows], targets[b_, c_][keep_rows]) if bool(keep_rows.any()) else leaf.new_zeros(()))
+        loss_pairs = torch.stack(pair).view(B, n_cls)
+        dl_g, = torch.autograd.grad(loss_pairs.sum(), leaf, allow_unused=True)
+    return loss_pairs.detach().reshape(-1), (torch.zeros_like(logits_g) if dl_g is None else dl_g).reshape(-1, 2).contiguous()
+
+
+def _clam_inst_forward(route, h, A, inst_w, inst_b, inst_cfg, B, N):
+    """Instance-level evaluation for ALL (bag, class) pairs at once (clam.py:103-132,150-168): the k top and k bottom patches of a bag
+    are the same rows for every class, so one gather, one stacked classifier GEMM and one grouped cross-entropy launch replace the
+    per-class / per-bag loops; pairs differ only in their targets (``_inst_constants``)
+    -> (inst_loss [B], ids [B,2k], predictions / targets [2,B,n_cls,2k], what the backward needs)"""
+    (labels, k, subtyping), dev, n_cls = inst_cfg[:3], h.device, inst_w.shape[0]
+    ids = ops.topk_ids(A, k)
+    lab = labels.to(device=dev, dtype=torch.int64) if isinstance(labels, torch.Tensor) else \
+        torch.as_tensor([int(v) for v in labels], dtype=torch.int64).to(dev)
+    w_st = inst_w.reshape(n_cls * 2, -1).contiguous()
+    if route.inst_fused:
+        # one launch: gather the 2k rows, all 2 n_cls instance logits, the cross-entropies and their gradients
+        inst_loss, dl, inst_pt = ops.clam_inst_fwd(h, ids, lab, w_st, inst_b.reshape(-1), B, N, k, n_cls, subtyping)
+        return inst_loss, ids, inst_pt, CLAMInstFused(ids, dl, w_st, k, n_cls)
+    base, cls_ids, t_in, t_out = _inst_constants(dev, B, N, k, n_cls, subtyping)
+    rows_all = (base + ids.to(torch.int64)).reshape(-1)                        # [B*2k] rows of h
+    feats = ops.take_rows(h, rows_all)                                         # [B*2k, L] f32
+    logits = ops.gemm_nt(feats, w_st, epi=ops.EPI_BIAS, bias=inst_b.reshape(-1).contiguous())   # [B*2k, 2 n_cls]
+    logits_g = logits.view(B, 2 * k, n_cls, 2).permute(0, 2, 1, 3).contiguous()                 # [B, n_cls, 2k, 2]
+    targets = torch.where((lab.view(B, 1) == cls_ids).unsqueeze(2), t_in, t_out).contiguous()   # [B, n_cls, 2k]
+    loss_g, dl_g, preds_g = ops.cross_entropy(logits_g.view(-1, 2), targets.view(-1), 2 * k)
+    if len(inst_cfg) > 3 and inst_cfg[3] is not None:                          # a caller-supplied instance_loss_fn (clam.py:64-65)
+        loss_g, dl_g = _clam_custom_inst_loss(inst_cfg[3], logits_g, targets)
+    scale = 1.0 / n_cls if subtyping else 1.0                                  # clam.py:167-168
+    inst_pt = torch.stack([preds_g.view(B, n_cls, 2 * k), targets], 0)         # -1 where a pair has no such row
+    return loss_g.view(B, n_cls).sum(1) * scale, ids, inst_pt, CLAMInstExplicit(rows_all, feats, dl_g, scale, k, n_cls)
+
+
+def _clam_dgrad(route, x2, h, U, A, M, dM, m1, wa, wb, wc, ka, kb, wab_t, B, N):
+    """Pooling, soft-max and gate backward, then dZ1 = (dU [Wa;Wb] + A (x) dM) * relu'(h) (h is already the dropped h: zero where dropped)
+    -> (dU, dwc, dbc, column sums of dU, dWab or None, dz1, column sums of dz1 or None).  dWab None: the node's two big weight gradients
+    wait for dz1 and share one grouped launch (``_clam_param_grads``), and dz1's column sums are its deferred partial rows - decided here only."""
+    L, D, gated = h.shape[1], wa.shape[0], wb is not None
+    if route.gate == "u":
+        # pooling + soft-max + gate backward in ONE pass over (h, U): sum_m A_m (h_m . dM) = M . dM, so ds_n = A_n (h_n . dM - M . dM)
+        # needs no reduction over the bag; U / dU - and wab_t [L, 2D] - in the interleaved column order of the forward
+        dU, dwc, dbc, dbab = ops.gated_score_bwd_il(U, wc.reshape(-1).contiguous(), ka, kb, h=h, dM=dM, Mp=M, A=A.view(-1), rows_per_bag=N)
+        # gate + first-layer weight gradients (clam.py:69-72) wait for dz1 and share one round of workgroups; the reduce launch
+        # also undoes the 16-row interleave, applies the Dropout factor and sums the bias-gradient rows (no ATen launches)
+        grouped = _GROUP_WGRAD and ops.gemm_tn_grouped_ok([(dU, h, None, None, None), (h, x2, None, None, None)])
+        dwab = None if grouped else ops.gemm_tn(dU, h).view(D // 16, 2, 16, L).permute(1, 0, 2, 3).reshape(2 * D, L)   # rows back in [Wa; Wb] order
+    else:
+        dA = ops.rows_dot(h.view(B, N, L), dM.view(B, 1, L)).view(B, N)           # pooling: dA[n] = h[n].dM ; soft-max backward ; gate backward
+        ds = ops.softmax_rows_bwd(A, dA).view(-1)
+        dU, dwc, dbc, dbab = ops.gated_score_bwd(U, wc.reshape(-1).contiguous(), ds, ka, kb, gated=gated)   # dbab: column sums, same pass
+        dwab = ops.gemm_tn(dU, h)                                                     # [2D, L] (gated) / [D, L]
+        wab_t = ops.transpose_cast(torch.cat([wa, wb], 0) if gated else wa, h.dtype)
+    if not route.dz1_panel:
+        return dU, dwc, dbc, dbab, dwab, ops.gemm_nt(dU, wab_t, epi=ops.EPI_RANK1_MASK, mask=h, rowscale=A.view(-1), rank1=dM, rows_per_bag=N), None
+    # column sums (the bias gradient) come out of the same launch; the instance branch extends them by the few rows it adds
+    dz1, _, db1 = ops.panel_gemm(dU, wab_t, ops.PG_RANK1_MASK, bitmask=m1 if m1 is not None else ops.relu_bitmask(h),
+                                 rowscale=A.view(-1), rank1=dM, rows_per_bag=N, colsum=True, colsum_defer=dwab is None)
+    return dU, dwc, dbc, dbab, dwab, dz1, db1
+
+
+def _clam_inst_backward(route, saved, h, dz1, dinst, inst_w, B, N, colsum_into):
+    """Instance branch: classifier gradients, and the sparse feature gradients added into dz1 under the same ReLU mask.  The panel dz1 product took its
+    column sums before these rows: theirs are added to ``colsum_into`` or, without one, returned -> (dW_inst [n_cls,2,L], db_inst [n_cls,2], those sums or None)."""
+    k, n_cls = saved.k, saved.n_cls
+    if route.inst_fused:
+        dwi, dbi, gsum = ops.clam_inst_bwd(h, saved.ids, saved.w_st, saved.dl, dinst.float(), B, N, k, n_cls, dz1)
+        if colsum_into is not None:
+            colsum_into.add_(gsum)
+    else:
+        up = (dinst * saved.scale).view(B, 1, 1, 1)                                # upstream weight per (bag, ...)
+        dlog = (saved.dl.view(B, n_cls, 2 * k, 2) * up).permute(0, 2, 1, 3).reshape(B * 2 * k, 2 * n_cls).contiguous()
+        dwi = ops.gemm_tn(dlog, saved.feats)                                       # (gemm_tn pads narrow N1 itself)
+        dbi = ops.colsum(dlog)
+        g = ops.gemm_nt(dlog, inst_w.reshape(n_cls * 2, -1).t().contiguous())      # [B*2k, L]; K = 2 n_cls is padded
+        ops.scatter_add_rows_masked(dz1, h, saved.rows, g, write_back=route.dz1_panel)
+        gsum = ops.colsum(g, out=colsum_into, accumulate=colsum_into is not None) if route.dz1_panel else None   # of the rows just added
+    return dwi.view(n_cls, 2, -1), dbi.view(n_cls, 2), None if colsum_into is not None else gsum
+
+
+def _clam_param_grads(dU, h, dz1, x2, dwab, db1, inst_sums, k1):
+    """-> (dW1, db1, dWab): the first layer's weight gradient - with the gate's in one grouped launch where that waited (``dwab`` None) - and
+    its bias gradient from ``db1`` (``_clam_dgrad``) and ``inst_sums``, what the instance branch added behind deferred sums; the Dropout factor on both."""
+    kp = None if k1 is None else k1.keep_q if isinstance(k1, ops.DropSeed) else 0.75      # the surviving entries of the keep mask all equal 1/0.75
+    if dwab is None:
+        parts, db1 = db1, torch.empty((h.shape[1],), dtype=torch.float32, device=dz1.device)
+        dwab, dw1 = ops.gemm_tn_grouped([(dU, h, None, None, None, {"deinterleave": True}),
+                                         (dz1, x2, None, db1, parts, dict({} if kp is None else {"scale": 1.0 / kp}, overwrite=True))], fresh=True)
+        if inst_sums is not None:
+            db1 = db1 + (inst_sums if kp is None else inst_sums / kp)
+        return dw1, db1, dwab
+    dw1 = ops.gemm_tn(dz1, x2)
+    if db1 is None:
+        db1 = ops.colsum(dz1)
+    return (dw1, db1, dwab) if kp is None else (dw1 / kp, db1 / kp, dwab)
+
+
+class CLAMFn(torch.autograd.Function):
+    """CLAM_SB.bag_forward for a batch of equal-length bags, optionally with the instance-level loss (models/clam.py:134-181,103-132).
+    x [B,N,d] in the compute dtype; parameters f32 (``wb`` / ``bb`` None: the plain ``Attn_Net`` of ``CLAM_SB(gate=False)``, clam.py:18-34,80-81).
+    ``keeps`` = None (eval) or the Dropout keeps of h, the tanh branch and the sigmoid branch (clam.py:71-72,47-48): three ``ops.DropSeed``s,
+    or three keep-multiplier tensors (values 0 or 1/0.75; parity tests).  ``inst_cfg`` = None or (labels: list[int] or tensor [B], k_sample,
+    subtyping[, instance_loss_fn]) with ``inst_w`` [n_cls,2,L], ``inst_b`` [n_cls,2]; ``grad_on``: see ABMILFn.forward.
+
+    ``clam_route`` picks every form once, in ``forward``; ``backward`` reads the stored route:
+      first layer  ``ops.panel_gemm`` (bf16, d = 512) or ``ops.gemm_nt``; its Dropout in that epilogue (panel kernel, seeds), in
+                   ``ops.dropout_relu_bitmask`` (seeds, B*N % 32 == 0), by ``ops.mul`` with an ``ops.dropout_mask`` or the caller's tensor;
+      gate         fused (bf16, L = 2D = 512, eval, no backward to follow): ``ops.panel_gate_score``, no pre-activations;
+                   u (the same shapes, no keep tensors, ``ops.gated_bwd_il_supported``): ``ops.panel_gate_u``, backward in one pass
+                   (``ops.gated_score_bwd_il``); both pool by ``ops.softmax_rows_parts`` + ``ops.weighted_rowsum(into=)``;
+                   panel / tile (``gate=False``, ``size_arg="big"``, keep tensors, f32): ``ops.panel_gemm`` or ``ops.gemm_nt``, then
+                   ``gated_score_fwd``, ``softmax_rows``, ``weighted_rowsum``; ``rows_dot``, ``softmax_rows_bwd``, ``gated_score_bwd`` back;
+      dz1          ``ops.panel_gemm(PG_RANK1_MASK)`` with its column sums (bf16, 512 gate columns) or ``ops.gemm_nt(EPI_RANK1_MASK)``;
+                   behind gate u the two big weight gradients go as one ``ops.gemm_tn_grouped`` where its plan groups them;
+      instance     one launch each way (``ops.clam_inst_fwd`` / ``clam_inst_bwd``: the default cross-entropy, n_cls <= 8, k <= 32), or
+                   ``take_rows``, ``gemm_nt``, ``cross_entropy`` [, the caller's loss on the host] and ``scatter_add_rows_masked`` back.
+    Returns (M [B,L], A [B,N], raw scores [B,N], inst_loss [B], ids [B,2k] int32, [2,B,n_cls,2k] int64: predictions and targets per (bag,
+    class), -1 where a pair has no such row); without ``inst_cfg`` the last three are zeros / empty.  Only M and inst_loss carry grad."""
 
     @staticmethod
     def forward(ctx, x, w1, b1, wa, ba, wb, bb, wc, bc, inst_w, inst_b, keeps, inst_cfg, grad_on=True):
-        B, N, d = x.shape
-        T = x.dtype
-        f32 = T == torch.float32
-        c = (lambda w: w) if f32 else (lambda w: ops.cast(w, T))
-        x2 = x.reshape(B * N, d)
-        L, D = w1.shape[0], wa.shape[0]
+        (B, N, d), T, dev = x.shape, x.dtype, x.device
+        k1, ka, kb = keeps if keeps is not None else (None, None, None)
         # bf16 gated chain: the compute-dtype copy of fc, the two gate Linears interleaved for the panel kernel and their transpose
-        # come out of ONE launch (none between optimizer steps) instead of a dozen cat / gather / cast launches
-        views = ops.clam_views(w1, wa, ba, wb, bb, wc, T) if (T == torch.bfloat16 and wb is not None and D % 16 == 0) else None
-        if views is not None:
-            c = lambda w: views[0] if w is w1 else ops.cast(w, T)          # noqa: E731
-        m1 = None
-        k1 = ka = kb = None
-        if keeps is not None:
-            k1, ka, kb = keeps
-        seeded = isinstance(k1, ops.DropSeed)
-        fc_drop = False
-        if T == torch.bfloat16 and d == 512 and ops.panel_supported(B * N, L, 512, ops.PG_BIAS_RELU):
-            # weight-stationary panel kernel; its 1-bit ReLU mask also serves the backward pass.  Seeded Dropout(0.25) behind the
-            # ReLU (clam.py:69-72) happens in the same epilogue: the mask is never materialised and the bits record what survives
-            fc_drop = _FUSED_FC_DROP and seeded
-            h, m1, _ = ops.panel_gemm(x2, c(w1), ops.PG_BIAS_RELU, bias=b1, want_bitmask=fc_drop or (keeps is None and bool(grad_on)),
-                                      drop=k1 if fc_drop else None)
-        else:
-            h = ops.gemm_nt(x2, c(w1), epi=ops.EPI_BIAS_RELU, bias=b1)                # clam.py:69
-        if keeps is not None and not fc_drop:
-            if seeded:                                                                 # Dropout(0.25) after ReLU (clam.py:69-72)
-                if (B * N) % 32 == 0 and L % 128 == 0:
-                    # the mask is generated inside the pass that applies it, which also leaves the 1-bit mask of the
-                    # surviving positive entries for the backward pass (bf16 panel dgrad)
-                    m1 = ops.dropout_relu_bitmask(h, k1, want_bits=(T == torch.bfloat16))
-                else:
-                    ops.mul(h, ops.dropout_mask(h.shape, T, k1.keep_p, h.device, seed=k1.seed))
-            else:
-                ops.mul(h, k1)                                                         # an injected keep mask (parity tests)
-        gated = wb is not None                   # False: the plain Attn_Net (CLAM_SB(gate=False), clam.py:18-34,80-81)
-        GW = 2 * D if gated else D               # gate columns
-        # bf16 with 512-wide h and gates: the weight-stationary panel kernel (same GEMM, half the time of the tile kernel)
-        panel = (T == torch.bfloat16 and L == 512 and ops.panel_supported(B * N, GW, 512, ops.PG_BIAS))
-        # (``grad_on`` = the caller's torch.is_grad_enabled(): see ABMILFn.forward)
-        fused_gate = (_FUSED_GATE and panel and gated and keeps is None and GW == 512 and not (grad_on and any(ctx.needs_input_grad))
-                      and ops.panel_supported(B * N, GW, 512, ops.PG_GATE))
-        # calls a backward pass may follow: the same epilogue also leaves the pre-activations (interleaved column order) for it,
-        # and the separate score pass over U (97-120 us at C3) disappears; the gate Dropouts are applied inside from their seeds
-        gate_u = (_GATE_U and not fused_gate and panel and gated and GW == 512 and (keeps is None or seeded)
-                  and ops.panel_supported(B * N, GW, 512, ops.PG_GATE_U) and ops.gated_bwd_il_supported(B * N, D, L, N)
-                  and ops.panel_supported(B * N, L, 512, ops.PG_RANK1_MASK, N))
-        if fused_gate:
-            # forward-only calls (validation, heat-map scoring, the frozen aggregator of stage 2): the score comes out of the gate
-            # GEMM's epilogue - tanh(a_d) sigmoid(b_d) c_d summed per wave - and the [B*N, 2D] pre-activations are never written
-            U = None
-            s_parts = ops.panel_gate_score(h, views[1], views[3], views[4], bc, parts=True)
-        elif gate_u:
-            U, s_parts = ops.panel_gate_u(h, views[1], views[3], views[4], bc, ka, kb, parts=True)
-        else:
-            wab = torch.cat([wa, wb], 0) if gated else wa
-            bab = torch.cat([ba, bb], 0) if gated else ba
-            if panel:
-                U, _, _ = ops.panel_gemm(h, c(wab), ops.PG_BIAS, bias=bab)              # both gate branches, one pass
-            else:
-                U = ops.gemm_nt(h, c(wab), epi=ops.EPI_BIAS, bias=bab)
-        if not fused_gate and not gate_u:
-            s = ops.gated_score_fwd(U, wc.reshape(-1).contiguous(), bc, ka, kb, gated=gated).view(B, N)
-        if fused_gate or gate_u:
-            # the epilogue's partial rows summed on the way, and the pooled rows cleared for the pass below: one launch
-            M = torch.empty((B, L), dtype=torch.float32, device=x.device)
-            s, A = ops.softmax_rows_parts(s_parts, B, N, zero=M)
-            ops.weighted_rowsum(h.view(B, N, L), A.view(B, N, 1), into=M)              # clam.py:170
-        else:
-            A = ops.softmax_rows(s)                                                    # clam.py:144
-            M = ops.weighted_rowsum(h.view(B, N, L), A.view(B, N, 1)).view(B, L)       # clam.py:170
-        dev = x.device
-        inst_loss = _zeros_const(dev, B) if inst_cfg is None else None          # (both instance branches below write their own)
-        saved_inst = None
-        ids = None
-        inst_pt = None
+        # come out of ONE launch (none between optimizer steps) instead of a dozen cat / gather / cast launches - ahead of the route, whose
+        # queries then run beside it (30 us more from an idle GPU to the first launch measured the other way round)
+        views = ops.clam_views(w1, wa, ba, wb, bb, wc, T) if (T == torch.bfloat16 and wb is not None and wa.shape[0] % 16 == 0) else None
+        route = clam_route(B, N, d, w1.shape[0], wa.shape[0], T, wb is not None,
+                           None if keeps is None else "seeds" if isinstance(k1, ops.DropSeed) else "tensors", bool(grad_on), any(ctx.needs_input_grad),
+                           None if inst_cfg is None else (inst_w.shape[0], inst_cfg[1], len(inst_cfg) > 3 and inst_cfg[3] is not None))
+        x2 = x.reshape(B * N, d)
+        c = (lambda w: views[0] if w is w1 else ops.cast(w, T)) if views is not None else (lambda w: w) if T == torch.float32 else (lambda w: ops.cast(w, T))
+        h, m1 = _clam_first_layer(route, x2, c(w1), b1, k1)
+        U, s, A, M = _clam_gate(route, h, B, N, (wa, ba, wb, bb, wc, bc), views, c, ka, kb)
         if inst_cfg is not None:
-            # instance-level evaluation for ALL (bag, class) pairs at once (clam.py:103-132,150-168): the k top and k
-            # bottom patches of a bag are the same rows for every class, so one gather, one stacked classifier GEMM and
-            # one grouped cross-entropy launch replace the per-class / per-bag loops; pairs differ only in their targets:
-            #   class == label      -> 2k rows, targets [1]*k + [0]*k            (inst_eval,     clam.py:105-119)
-            #   class != label      -> k top rows with target 0 if subtyping    (inst_eval_out, clam.py:122-132), else none
-            labels, k, subtyping = inst_cfg[:3]
-            custom_loss = inst_cfg[3] if len(inst_cfg) > 3 else None          # a caller-supplied instance_loss_fn (clam.py:64-65,118,131)
-            n_cls = inst_w.shape[0]
-            ids = ops.topk_ids(A, k)                                                   # [B, 2k]
-            lab = labels.to(device=dev, dtype=torch.int64) if isinstance(labels, torch.Tensor) else \
-                torch.as_tensor([int(v) for v in labels], dtype=torch.int64).to(dev)
-            w_st = inst_w.reshape(n_cls * 2, -1).contiguous()
-            if custom_loss is None and _FUSED_INST and 2 * n_cls <= 16 and k <= 32 and L % 8 == 0:
-                # one launch: gather the 2k rows, all 2 n_cls instance logits, the cross-entropies and their gradients
-                inst_loss, dl, inst_pt = ops.clam_inst_fwd(h, ids, lab, w_st, inst_b.reshape(-1), B, N, k, n_cls, subtyping)
-                saved_inst = ("fused", ids, dl, w_st, k, n_cls)
-            else:
-                base, cls_ids, t_in, t_out = _inst_constants(dev, B, N, k, n_cls, subtyping)
-                rows_all = (base + ids.to(torch.int64)).reshape(-1)                        # [B*2k] rows of h
-                feats = ops.take_rows(h, rows_all)                                         # [B*2k, L] f32
-                logits = ops.gemm_nt(feats, w_st, epi=ops.EPI_BIAS, bias=inst_b.reshape(-1).contiguous())   # [B*2k, 2 n_cls]
-                logits_g = logits.view(B, 2 * k, n_cls, 2).permute(0, 2, 1, 3).contiguous()                 # [B, n_cls, 2k, 2]
-                same = lab.view(B, 1) == cls_ids                                                            # [B, n_cls]
-                targets = torch.where(same.unsqueeze(2), t_in, t_out).contiguous()                          # [B, n_cls, 2k]
-                loss_g, dl_g, preds_g = ops.cross_entropy(logits_g.view(-1, 2), targets.view(-1), 2 * k)
-                if custom_loss is not None:
-                    # The reference hands (logits [rows,2], targets [rows]) of every evaluated (bag, class) pair to whatever loss it was
-                    # constructed with (clam.py:118,131).  The gather, the classifier product and the predictions above are the HIP
-                    # kernels; the caller's loss runs on the pair's few logits as given (rows with target -1 do not exist for that pair)
-                    # and its gradient w.r.t. them - taken here with autograd on that [rows,2] leaf - takes the place of the
-                    # cross-entropy gradient in the backward pass below.  A loss with parameters of its own gets no gradient for them.
-                    with torch.enable_grad():
-                        leaf = logits_g.detach().requires_grad_()
-                        tg = targets.view(B, n_cls, 2 * k)
-                        pair = []
-                        for b_ in range(B):
-                            for c_ in range(n_cls):
-                                keep_rows = tg[b_, c_] >= 0
-                                if bool(keep_rows.any()):
-                                    pair.append(custom_loss(leaf[b_, c_][keep_rows], tg[b_, c_][keep_rows]))
-                                else:
-                                    pair.append(leaf.new_zeros(()))
-                        loss_pairs = torch.stack(pair).view(B, n_cls)
-                        dl_g, = torch.autograd.grad(loss_pairs.sum(), leaf, allow_unused=True)
-                    loss_g = loss_pairs.detach().reshape(-1)
-                    dl_g = (torch.zeros_like(logits_g) if dl_g is None else dl_g).reshape(-1, 2).contiguous()
-                scale = 1.0 / n_cls if subtyping else 1.0                                  # clam.py:167-168
-                inst_loss = loss_g.view(B, n_cls).sum(1) * scale
-                inst_pt = torch.stack([preds_g.view(B, n_cls, 2 * k), targets], 0)         # -1 where a pair has no such row
-                saved_inst = (rows_all, feats, dl_g, scale, k, n_cls)
+            inst_loss, ids, inst_pt, saved_inst = _clam_inst_forward(route, h, A, inst_w, inst_b, inst_cfg, B, N)
+        else:
+            # the cached zero is shared by every call without an instance branch: as a differentiable output autograd would re-point its
+            # grad_fn at this node (keeping the node's saved activations alive through the cache) - hand out a view, marked non-differentiable
+            inst_loss, saved_inst = _zeros_const(dev, B).detach()[:], None
+            ids, inst_pt = torch.zeros((B, 0), dtype=torch.int32, device=dev), torch.zeros((2, B, 0, 0), dtype=torch.int64, device=dev)
         ctx.save_for_backward(x2, h, U if U is not None else _placeholder(x2), A, M, w1, wa, wb, wc,
                               inst_w if inst_w is not None else _placeholder(x2), m1)
-        ctx.gated, ctx.gate_u = gated, gate_u
         ctx.bias_params = (b1, ba, bb, bc)               # (the parameters themselves: the backward pass adds into their gradient buffers)
-        ctx.wab_t = views[2] if gate_u else None         # (a cached view: parameters do not change between a forward and its backward)
-        ctx.keeps, ctx.saved_inst, ctx.dims = keeps, saved_inst, (B, N, d, L, D)
-        if ids is None:
-            ids = torch.zeros((B, 0), dtype=torch.int32, device=dev)
-        if inst_pt is None:
-            inst_pt = torch.zeros((2, B, 0, 0), dtype=torch.int64, device=dev)
-        if inst_cfg is None:
-            # the cached zero is shared by every call without an instance branch: as a differentiable output autograd would
-            # re-point its grad_fn at this node (keeping the node's saved activations alive through the cache) - hand out a view,
-            # marked non-differentiable
-            inst_loss = inst_loss.detach()[:]
-            ctx.mark_non_differentiable(A, s, ids, inst_pt, inst_loss)
-        else:
-            ctx.mark_non_differentiable(A, s, ids, inst_pt)
+        ctx.wab_t = views[2] if route.gate == "u" else None   # (a cached view: parameters do not change between a forward and its backward)
+        ctx.route, ctx.keeps, ctx.saved_inst, ctx.dims = route, keeps, saved_inst, (B, N)
+        ctx.mark_non_differentiable(A, s, ids, inst_pt, *((inst_loss,) if inst_cfg is None else ()))
         ctx.set_materialize_grads(False)
         return M, A, s, inst_loss, ids, inst_pt
 
@@ -1261,96 +1336,20 @@ class CLAMFn(torch.autograd.Function):
     def backward(ctx, dM, _dA, _ds, dinst, _dids, _dpt):
         _enter(ctx)
         x2, h, U, A, M, w1, wa, wb, wc, inst_w, m1 = ctx.saved_tensors
-        b1, ba, bb, bc = ctx.bias_params
-        B, N, d, L, D = ctx.dims
-        T = x2.dtype
-        f32 = T == torch.float32
-        c = (lambda t: t) if f32 else (lambda t: ops.cast(t, T))
-        k1 = ka = kb = None
-        if ctx.keeps is not None:
-            k1, ka, kb = ctx.keeps
+        (b1, ba, bb, bc), route, (B, N), D = ctx.bias_params, ctx.route, ctx.dims, wa.shape[0]
+        k1, ka, kb = ctx.keeps if ctx.keeps is not None else (None, None, None)
         dM = dM.contiguous() if dM is not None else torch.zeros_like(M)
-        gated = ctx.gated
-        if ctx.gate_u:
-            # pooling + soft-max + gate backward in ONE pass over (h, U): sum_m A_m (h_m . dM) = M . dM, so
-            # ds_n = A_n (h_n . dM - M . dM) needs no reduction over the bag; U / dU in the interleaved column order of the forward
-            dU, dwc, dbc, dbab = ops.gated_score_bwd_il(U, wc.reshape(-1).contiguous(), ka, kb, h=h, dM=dM, Mp=M, A=A.view(-1),
-                                                        rows_per_bag=N)
-            # gate + first-layer weight gradients (clam.py:69-72) wait for dz1 and share one round of workgroups; the reduce launch
-            # also undoes the 16-row interleave, applies the Dropout factor and sums the bias-gradient rows (no ATen launches)
-            grouped = _GROUP_WGRAD and ops.gemm_tn_grouped_ok([(dU, h, None, None, None), (h, x2, None, None, None)])
-            dwab = None
-            if not grouped:
-                dwab = ops.gemm_tn(dU, h).view(D // 16, 2, 16, L).permute(1, 0, 2, 3).reshape(2 * D, L)   # rows back in [Wa; Wb] order
-            wab_t = ctx.wab_t                                                         # [L, 2D] interleaved columns, as dU's
-        else:
-            # pooling: dA[n] = h[n].dM ; soft-max backward ; gate backward
-            dA = ops.rows_dot(h.view(B, N, L), dM.view(B, 1, L)).view(B, N)
-            ds = ops.softmax_rows_bwd(A, dA).view(-1)
-            dU, dwc, dbc, dbab = ops.gated_score_bwd(U, wc.reshape(-1).contiguous(), ds, ka, kb, gated=gated)   # dbab: column sums, same pass
-            dwab = ops.gemm_tn(dU, h)                                                     # [2D, L] (gated) / [D, L]
-            wab_t = None
-            grouped = False
-        wab = None if wab_t is not None else (torch.cat([wa, wb], 0) if gated else wa)
-        # dZ1 = (dU [Wa;Wb] + A (x) dM) * relu'(h)   (h here is already the dropped h: zero where dropped)
-        if (T == torch.bfloat16 and dU.shape[1] == 512 and ops.panel_supported(B * N, L, 512, ops.PG_RANK1_MASK, N)):
-            # column sums (the bias gradient) come out of the same launch; the instance branch below extends them by the
-            # few rows it adds
-            dz1, _, db1 = ops.panel_gemm(dU, wab_t if wab_t is not None else ops.transpose_cast(wab, T), ops.PG_RANK1_MASK,
-                                         bitmask=m1 if m1 is not None else ops.relu_bitmask(h),
-                                         rowscale=A.view(-1), rank1=dM, rows_per_bag=N, colsum=True, colsum_defer=grouped)
-            db1_parts = db1 if grouped else None
-        else:
-            db1 = db1_parts = None
-            assert not grouped
-            dz1 = ops.gemm_nt(dU, ops.transpose_cast(wab, T), epi=ops.EPI_RANK1_MASK, mask=h, rowscale=A.view(-1),
-                              rank1=dM, rows_per_bag=N)
-        # instance branch: classifier grads + sparse feature grads added under the same ReLU mask
-        dinst_w = dinst_b = db1_extra = None
-        if ctx.saved_inst is not None and dinst is not None and ctx.saved_inst[0] == "fused":
-            _, ids, dl, w_st, k, n_cls = ctx.saved_inst
-            dwi, dbi, gsum = ops.clam_inst_bwd(h, ids, w_st, dl, dinst.float(), B, N, k, n_cls, dz1)
-            dinst_w, dinst_b = dwi.view(n_cls, 2, -1), dbi.view(n_cls, 2)
-            if grouped:
-                db1_extra = gsum
-            elif db1 is not None:
-                db1 = db1 + gsum
-        elif ctx.saved_inst is not None and dinst is not None:
-            rows_all, feats, dl_g, scale, k, n_cls = ctx.saved_inst
-            up = (dinst * scale).view(B, 1, 1, 1)                                      # upstream weight per (bag, ...)
-            dlog = (dl_g.view(B, n_cls, 2 * k, 2) * up).permute(0, 2, 1, 3).reshape(B * 2 * k, 2 * n_cls).contiguous()
-            dinst_w = ops.gemm_tn(dlog, feats).view(n_cls, 2, -1)                      # (gemm_tn pads narrow N1 itself)
-            dinst_b = ops.colsum(dlog).view(n_cls, 2)
-            g = ops.gemm_nt(dlog, inst_w.reshape(n_cls * 2, -1).t().contiguous())      # [B*2k, L]; K = 2 n_cls is padded
-            ops.scatter_add_rows_masked(dz1, h, rows_all, g, write_back=db1 is not None)
-            if grouped:
-                db1_extra = ops.colsum(g)
-            elif db1 is not None:
-                ops.colsum(g, out=db1, accumulate=True)                                  # [B*2k, L] f32: the rows just added
-        kp = None
-        if k1 is not None:                       # the surviving entries of the keep mask all equal 1/0.75
-            kp = k1.keep_q if isinstance(k1, ops.DropSeed) else 0.75
-        if grouped:
-            db1 = torch.empty((L,), dtype=torch.float32, device=dz1.device)
-            sc = None if kp is None else {"scale": 1.0 / kp}
-            dwab, dw1 = ops.gemm_tn_grouped([(dU, h, None, None, None, {"deinterleave": True}),
-                                             (dz1, x2, None, db1, db1_parts, dict(sc or {}, overwrite=True))], fresh=True)
-            if db1_extra is not None:            # the rows the instance branch added to dz1 after its column sums were taken
-                db1 = db1 + (db1_extra if kp is None else db1_extra / kp)
-        else:
-            dw1 = ops.gemm_tn(dz1, x2)
-            if db1 is None:
-                db1 = ops.colsum(dz1)
-            if kp is not None:
-                dw1, db1 = dw1 / kp, db1 / kp
+        dU, dwc, dbc, dbab, dwab, dz1, db1 = _clam_dgrad(route, x2, h, U, A, M, dM, m1, wa, wb, wc, ka, kb, ctx.wab_t, B, N)
+        dinst_w = dinst_b = inst_sums = None
+        if ctx.saved_inst is not None and dinst is not None:
+            dinst_w, dinst_b, inst_sums = _clam_inst_backward(route, ctx.saved_inst, h, dz1, dinst, inst_w, B, N, None if dwab is None else db1)
+        dw1, db1, dwab = _clam_param_grads(dU, h, dz1, x2, dwab, db1, inst_sums, k1)
+        gate = [(dwab, wa), (dbab.contiguous(), ba)] if wb is None else \
+            [(dwab[:D].contiguous(), wa), (dbab[:D].contiguous(), ba), (dwab[D:].contiguous(), wb), (dbab[D:].contiguous(), bb)]
         # the eight (six without the gate) parameter gradients: added to the optimizer's pre-seated buffers by ONE launch (autograd's
         # AccumulateGrad would run one ATen add per parameter); parameters without such a buffer get their tensors back
-        if not gated:
-            dw1, db1, dwab, dbab_, dwc_, dbc = _pgrads((dw1, w1), (db1, b1), (dwab, wa), (dbab.contiguous(), ba), (dwc.view(1, -1), wc), (dbc, bc))
-            return (None, dw1, db1, dwab, dbab_, None, None, dwc_, dbc, dinst_w, dinst_b, None, None, None)
-        dw1, db1, dwa_, dba_, dwb_, dbb_, dwc_, dbc = _pgrads((dw1, w1), (db1, b1), (dwab[:D].contiguous(), wa), (dbab[:D].contiguous(), ba),
-                                                              (dwab[D:].contiguous(), wb), (dbab[D:].contiguous(), bb), (dwc.view(1, -1), wc), (dbc, bc))
-        return (None, dw1, db1, dwa_, dba_, dwb_, dbb_, dwc_, dbc, dinst_w, dinst_b, None, None, None)
+        dw1, db1, *dgate, dwc, dbc = _pgrads((dw1, w1), (db1, b1), *gate, (dwc.view(1, -1), wc), (dbc, bc))
+        return (None, dw1, db1, *dgate, *([None, None] if wb is None else []), dwc, dbc, dinst_w, dinst_b, None, None, None)
 
 
 class PolicyHeadFn(torch.autograd.Function):
