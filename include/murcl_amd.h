@@ -588,6 +588,24 @@ int murcl_kmeans_step_wide(const float* X, int N, int d, int K, float* centers, 
  * multiple of 32 (else -1).  murcl_gemm_nt's bag-level form with its reduction kept unsplit whatever the deterministic mode (which is
  * not read): one writer per element, so a seeding picks the same centres on every run, on small slides of d >= 1536 too. */
 int murcl_kmeans_cross(const float* rows, int R, const float* X, int N, int d, float* out, murcl_stream_t stream);
+/* scikit-learn's greedy k-means++ seeding (_kmeans_plusplus behind KMeans(n_clusters, random_state=985).fit,
+ * wsi_processing/features_clustering.py:10-16) from scikit-learn's own draws, with no host round trip: the host takes `first` (the
+ * row of the first centre) and `uniforms` [K-1][T] f64 (device memory; T = 2 + int(log K) candidates per step) from numpy's
+ * RandomState; per step the device forms T candidate rows (inclusive f64 scan of the closest squared distances, left searchsorted
+ * of uniform * potential, clipped to N-1), the squared distances of every row to them (f64 sums, clamped at 0, rounded to f32: the
+ * float32 path of scikit-learn's euclidean_distances), the minimum with the closest distances and each candidate's potential (f64,
+ * fixed order), and keeps the first candidate of lowest potential.  X [N,d] f32, any d >= 1, 1 <= K <= 64, N >= K, 0 <= first < N
+ * (else -1, no launch).  -> indices [K] int32 (rows of X), centers [K,d] (those rows).  3K launches on `stream`, no float
+ * atomics, the deterministic mode is not read: the same bits on every run.
+ * workspace: murcl_kmeans_pp_workspace_bytes(N, d, K) (-1 for a shape the entry refuses), 16-byte aligned. */
+long murcl_kmeans_pp_workspace_bytes(int N, int d, int K);
+int murcl_kmeans_pp(const float* X, int N, int d, int K, int first, const double* uniforms, int* indices, float* centers,
+                    void* workspace, murcl_stream_t stream);
+/* The centring KMeans.fit runs before seeding and Lloyd (features_clustering.py:10-16; sklearn subtracts X.mean(axis=0) and adds
+ * it back to the centres): mean [d] = column means summed in f64 in a fixed order and rounded to f32, Xc [N,d] = X - mean in f32.
+ * Any N >= 1, d >= 1.  workspace: murcl_kmeans_center_workspace_bytes(N, d), 16-byte aligned. */
+long murcl_kmeans_center_workspace_bytes(int N, int d);
+int murcl_kmeans_center(const float* X, int N, int d, float* Xc, float* mean, void* workspace, murcl_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,10 @@ SIGNATURES = {
     "murcl_kmeans_wide_workspace_bytes": [_I, _I, _I],
     "murcl_kmeans_step_wide": [_P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P],
     "murcl_kmeans_cross": [_P, _I, _P, _I, _I, _P, _P],
+    "murcl_kmeans_pp_workspace_bytes": [_I, _I, _I],
+    "murcl_kmeans_pp": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "murcl_kmeans_center_workspace_bytes": [_I, _I],
+    "murcl_kmeans_center": [_P, _I, _I, _P, _P, _P, _P],
     "murcl_abmil_pool_combine": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "murcl_abmil_pool_decoder": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "murcl_abmil_pool_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
@@ -131,7 +135,8 @@ SIGNATURES = {
     "murcl_replay_tick": [_P, _P],
     "murcl_sgd_step": [_P, _P, _P, _L, _F, _F, _I, _F, _I, _I, _P],
 }
-_RESTYPE = {"murcl_ntxent_workspace_bytes": _L, "murcl_ntxent_xchg_bytes": _L, "murcl_kmeans_workspace_bytes": _L, "murcl_kmeans_wide_workspace_bytes": _L, "murcl_ppo_act_workspace": _L, "murcl_gemm_tn_plan": _L,
+_RESTYPE = {"murcl_ntxent_workspace_bytes": _L, "murcl_ntxent_xchg_bytes": _L, "murcl_kmeans_workspace_bytes": _L, "murcl_kmeans_wide_workspace_bytes": _L, "murcl_kmeans_pp_workspace_bytes": _L,
+            "murcl_kmeans_center_workspace_bytes": _L, "murcl_ppo_act_workspace": _L, "murcl_gemm_tn_plan": _L,
             "murcl_ppo_epoch_workspace": _L, "murcl_float_atomic_launches": _L, "murcl_colsum_workspace": _L,
             "murcl_weighted_rowsum_workspace": _L, "murcl_dsmil_attn_bwd_workspace": _L}
 

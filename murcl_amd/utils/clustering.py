@@ -6,10 +6,17 @@ input of ``WSIWithCluster``).  The reference runs scikit-learn's KMeans(random_s
 per slide; here Lloyd's iterations run on the HIP kernels, without float atomics, so a run is reproducible bit for bit:
 ``murcl_kmeans_step`` (one pass over the slide's features per iteration) for d in 256 / 512 / 1024 with at most 16 clusters,
 ``murcl_kmeans_step_wide`` (the same step tiled over d) for every other width - 2048 and 4096 of the reference's ResNet-50 /
-VGG-16 extractors, 384 / 768 / 1280 ... - and up to 64 clusters.  scikit-learn's random stream cannot be reproduced, so the partitions are
-not the reference's label for label; what is pinned (tests) is that from the SAME initial centres the iterations are
-scikit-learn's Lloyd iterations (same labels, centres and inertia), and that k-means++ seeding + restarts reach the
-same inertia range.
+VGG-16 extractors, 384 / 768 / 1280 ... - and up to 64 clusters.  Two seedings: ``seeding="native"`` (the default) draws from torch's
+generator, so its partitions are not the reference's label for label; what is pinned (tests) is that from the SAME initial centres
+the iterations are scikit-learn's Lloyd iterations (same labels, centres and inertia), and that k-means++ seeding + restarts reach
+the same inertia range.  ``seeding="sklearn"`` reproduces scikit-learn's stream: the draws of ``_kmeans_plusplus`` come from a host
+``numpy.random.RandomState(seed)`` exactly as scikit-learn (>= 1.3) takes them, the arithmetic on the features runs on the device at
+scikit-learn's precision (``murcl_kmeans_pp``: f64 sums, f32 distances), X is centred as ``KMeans.fit`` centres it
+(``murcl_kmeans_center``) and restarts are kept by scikit-learn's rule.  The partition is then scikit-learn's label for label
+WHENEVER no draw lands within rounding distance of a boundary of the cumulative sum and no argmin is a near-tie: scikit-learn adds
+its potential in f32 through BLAS, in an order that cannot be copied, so a draw flips with probability of roughly N x (relative
+error of that sum); that rate has not been measured at N in the tens of thousands, and the match is no guarantee for every slide.
+The line numbers cited below are those of sklearn/cluster/_kmeans.py in scikit-learn 1.7.2.
 """
 import json
 
@@ -128,11 +135,101 @@ def kmeans_plusplus(X, K, generator):
     return torch.stack(centers, 0)
 
 
-def kmeans(X, num_clusters, seed=985, n_init=3, max_iter=300, tol=1e-4):
-    """Best of ``n_init`` k-means++ starts by inertia.  -> (labels int32 [N], centers, inertia)."""
+SEEDINGS = ("native", "sklearn")
+
+
+def sklearn_draws(rs, N, K):
+    """The draws scikit-learn's ``_kmeans_plusplus`` takes from ``rs`` (a ``numpy.random.RandomState``) for one seeding of K centres
+    among N rows of float32 features, in its order.  -> (row of the first centre, uniforms float64 [K-1, 2 + int(log K)]).
+    _kmeans.py:225: the first centre is ``rs.choice(N, p=sample_weight / sample_weight.sum())`` with the float32 unit weights
+    ``KMeans.fit`` / ``kmeans_plusplus`` build for float32 features (:1467); :222, :243: every later step draws
+    ``rs.uniform(size=2 + int(log K))`` (consecutive doubles of the stream, so one [K-1, trials] draw is the same stream).  Lloyd takes
+    no draw, so the seedings of consecutive restarts are consecutive calls.  scikit-learn before 1.3 drew the first centre with
+    ``rs.randint(N)``: that variant is not built."""
+    w = np.ones(N, dtype=np.float32)
+    first = int(rs.choice(N, p=w / w.sum()))
+    return first, rs.uniform(size=(K - 1, 2 + int(np.log(K))))
+
+
+def _check_sklearn_shape(X, K):
+    if not X.is_cuda:
+        raise RuntimeError("murcl_amd k-means runs on the GPU only (no CPU fallback)")
+    if X.dim() != 2 or not 1 <= K <= 64 or X.shape[0] < K or X.shape[1] < 1:
+        raise ValueError(f"k-means++ with scikit-learn's stream takes [N,d] features, 1..64 clusters and N >= K (got X {tuple(X.shape)}, K = {K})")
+
+
+def _seed_sklearn(X, K, first, uniforms):
+    """One seeding on the device from the host's draws: K steps enqueued back to back, no host sync. -> (centers [K,d], indices int32 [K], both on the device)."""
+    N, d = X.shape
+    L = _lib.lib()
+    u = torch.from_numpy(np.ascontiguousarray(uniforms, dtype=np.float64).reshape(-1)).to(X.device) if K > 1 else None
+    indices = torch.empty((K,), dtype=torch.int32, device=X.device)
+    centers = torch.empty((K, d), dtype=torch.float32, device=X.device)
+    ws = torch.empty(((L.murcl_kmeans_pp_workspace_bytes(N, d, K) + 15) // 16, 2), dtype=torch.float64, device=X.device)
+    check(L.murcl_kmeans_pp(ptr(X), N, d, K, first, ptr(u), ptr(indices), ptr(centers), ptr(ws), stream()), "kmeans_pp")
+    return centers, indices
+
+
+def kmeans_plusplus_sklearn(X, K, seed):
+    """``sklearn.cluster.kmeans_plusplus(X, K, random_state=seed)`` (scikit-learn >= 1.3) on the device: X [N,d] f32 cuda as given (not
+    centred, like that function), ``seed`` an int or a ``numpy.random.RandomState`` (left where scikit-learn would leave it).
+    -> (centers [K,d] on the device, indices int64 numpy [K]); the indices are read back once, after the last step."""
+    X = X.float().contiguous()
+    _check_sklearn_shape(X, K)
+    rs = seed if isinstance(seed, np.random.RandomState) else np.random.RandomState(seed)
+    centers, indices = _seed_sklearn(X, K, *sklearn_draws(rs, X.shape[0], K))
+    return centers, indices.cpu().numpy().astype(np.int64)
+
+
+def _center(X):
+    """_kmeans.py:1477-1481: -> (X - column mean, column mean), on the device (mean in f64, rounded to f32)."""
+    N, d = X.shape
+    L = _lib.lib()
+    Xc, mean = torch.empty_like(X), torch.empty((d,), dtype=torch.float32, device=X.device)
+    ws = torch.empty(((L.murcl_kmeans_center_workspace_bytes(N, d) + 7) // 8,), dtype=torch.float64, device=X.device)
+    check(L.murcl_kmeans_center(ptr(X), N, d, ptr(Xc), ptr(mean), ptr(ws), stream()), "kmeans_center")
+    return Xc, mean
+
+
+def _is_same_clustering(a, b, K):
+    """_k_means_common.pyx:314-328: is every label of ``a`` mapped onto one label of ``b``?"""
+    pairs = np.unique(a.astype(np.int64) * K + b.astype(np.int64))
+    return len(np.unique(pairs // K)) == len(pairs)
+
+
+def _kmeans_sklearn(X, K, seed, n_init, max_iter, tol):
+    """``KMeans(K, random_state=seed, n_init=n_init).fit(X)`` (_kmeans.py:1466-1553): centre, then per restart seed and iterate; a later
+    restart replaces the best only if its inertia is strictly lower and its partition differs up to relabelling (:1525-1528)."""
+    _check_sklearn_shape(X, K)
+    rs = np.random.RandomState(seed)
+    draws = [sklearn_draws(rs, X.shape[0], K) for _ in range(n_init)]          # Lloyd takes no draw: all restarts up front, in order
+    Xc, mean = _center(X)
+    best = best_lab = None
+    for first, uniforms in draws:
+        out = lloyd(Xc, _seed_sklearn(Xc, K, first, uniforms)[0], max_iter, tol)
+        lab = out[0].cpu().numpy()
+        if best is None or (out[2] < best[2] and not _is_same_clustering(lab, best_lab, K)):
+            best, best_lab = out, lab
+    return best[0], best[1] + mean, best[2]
+
+
+def kmeans(X, num_clusters, seed=985, n_init=None, max_iter=300, tol=1e-4, seeding="native"):
+    """Best of ``n_init`` k-means++ starts by inertia.  -> (labels int32 [N], centers, inertia).
+    ``seeding="native"`` (default; ``n_init`` defaults to 3) draws from torch's generator.  ``seeding="sklearn"`` reproduces
+    ``KMeans(num_clusters, random_state=seed, n_init=n_init)`` of scikit-learn >= 1.3 (see the module docstring for the limit of that
+    claim); there ``n_init`` defaults to 1, what ``n_init='auto'`` means for k-means++ (_kmeans.py:879-881) - a run of the reference
+    made with an older scikit-learn is reproduced with ``n_init=10``."""
+    if seeding not in SEEDINGS:
+        raise ValueError(f"seeding is one of {SEEDINGS}, got {seeding!r}")
+    if n_init is None:
+        n_init = 3 if seeding == "native" else 1
+    if n_init < 1:
+        raise ValueError(f"n_init >= 1, got {n_init}")
+    X = X.float().contiguous()
+    if seeding == "sklearn":
+        return _kmeans_sklearn(X, num_clusters, seed, n_init, max_iter, tol)
     g = torch.Generator(device=X.device)
     g.manual_seed(seed)
-    X = X.float().contiguous()
     best = None
     for _ in range(n_init):
         out = lloyd(X, kmeans_plusplus(X, num_clusters, g), max_iter, tol)
@@ -141,10 +238,11 @@ def kmeans(X, num_clusters, seed=985, n_init=3, max_iter=300, tol=1e-4):
     return best[0], best[1], best[2]
 
 
-def clustering(feats, num_clusters, filepath=None, device="cuda", seed=985):
-    """features_clustering.py:10-16: -> ``features_cluster_indices`` int array [N,1]; saved to ``filepath`` (npz) if given."""
+def clustering(feats, num_clusters, filepath=None, device="cuda", seed=985, seeding="native", n_init=None):
+    """features_clustering.py:10-16: -> ``features_cluster_indices`` int array [N,1]; saved to ``filepath`` (npz) if given.
+    ``seeding="sklearn"``: the partition of the reference's ``KMeans(num_clusters, random_state=seed)`` (see ``kmeans``)."""
     X = torch.as_tensor(np.asarray(feats, dtype=np.float32)) if not isinstance(feats, torch.Tensor) else feats
-    labels, _, _ = kmeans(X.to(device), num_clusters, seed=seed)
+    labels, _, _ = kmeans(X.to(device), num_clusters, seed=seed, n_init=n_init, seeding=seeding)
     idx = labels.cpu().numpy().astype(np.int64).reshape(-1, 1)
     if filepath is not None:
         np.savez(file=filepath, features_cluster_indices=idx)
